@@ -35,7 +35,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SSDN_ABI_VERSION 14
+#define SSDN_ABI_VERSION 15
 #define SSDN_MAX_TAPS 9
 
 /* NHWC fp16 view: element (n,y,x,c) lives at p[((n*H + y)*W + x)*cs + co + c]. */
@@ -67,7 +67,8 @@ enum ssdn_op_type {
     SSDN_OP_ZERO = 19,
     SSDN_OP_EVENT_RECORD = 20, /* hipEventRecord(event) on the op's lane: lets a consumer outside the list (the gradient
                                   all-reduce on its own stream) wait for a PREFIX of the list */
-    SSDN_OP_NOISE = 21         /* training patch stream: uint8 clean patches -> noisy / clean / reference fp32 (+ Noise2Void) */
+    SSDN_OP_NOISE = 21,        /* training patch stream: uint8 clean patches -> noisy / clean / reference fp32 (+ Noise2Void) */
+    SSDN_OP_INPUT_GRAD = 22    /* gradient w.r.t. the network input (NoiseNetwork under autograd with x.requires_grad) */
 };
 
 /* One record of the op list.  `args` points at the matching ssdn_*_args struct (host memory).
@@ -464,6 +465,31 @@ typedef struct ssdn_noise_args {
     int32_t n2v_radius;   /* sub-patch radius (2 for the reference's 5 x 5) */
     uint64_t seed, offset;
 } ssdn_noise_args;
+
+/* ---- SSDN_OP_INPUT_GRAD --------------------------------------------------------------------
+ * replaces: the data gradient autograd propagates into the network input through the first conv (noise_network.py:69-71) and the
+ * skip half of decode_block_1's first conv (torch.cat with the input, noise_network.py:203-205), then back through the 4-rotation
+ * stacking (noise_network.py:187-189).  The packed input x16 (SSDN_OP_PACK_INPUT) feeds exactly these two layers, so
+ *     dx[b,c,y,x] = sum_r sum_t [ sum_{k<48} g_e0 [rB+b, p_r(y,x) - tap_t, k] * We[k][c][t]
+ *                               + sum_{k<96} g_d1a[rB+b, p_r(y,x) - tap_t, k] * Wd[k][96+c][t] ]
+ * with p_r the rotated position of (y,x) in rotation r (SSDN_OP_PACK_INPUT's map), tap_t = (dy[t], dx[t]) the forward taps and
+ * zeros outside the image.  g_e0 / g_d1a are the PRE-activation gradients of the two layers (bf16, as the backward list leaves them).
+ * The weights are read from the fp32 master buffer and rounded to bf16 inside the kernel -- the operand precision of every other data
+ * gradient (the wd shadows of SSDN_OP_WPACK are bf16); accumulation is fp32.  Gather form: every output element is written once by one
+ * thread, in a fixed order over (r, t, k) -- bit-reproducible, no atomics, no partial buffers.
+ * Requirements: 1 <= C <= 3, R in {1, 4} (4: H == W), H and W multiples of 16, nine taps spanning at most 3 x 3, 16-byte aligned views
+ * (cs, co multiples of 8) with 48 / 96 channels. */
+typedef struct ssdn_input_grad_args {
+    ssdn_view g_e0;      /* bf16 [R*B,H,W,cs] pre-activation gradient of encode_block_1.0 (48 channels) */
+    ssdn_view g_d1a;     /* bf16 [R*B,H,W,cs] pre-activation gradient of decode_block_1.0 (96 channels) */
+    const float* w_e;    /* fp32 OIHW [48][C][3][3]: encode_block_1.0 */
+    const float* w_d;    /* fp32 OIHW [96][96+C][3][3]: decode_block_1.0 (input channels 96.. are the network input) */
+    float* out;          /* [B,C,H,W] fp32 (overwritten) */
+    int32_t B, C, H, W;
+    int32_t R;           /* 4 (blind-spot) or 1 */
+    int32_t ntaps;       /* 9 */
+    int32_t dy[SSDN_MAX_TAPS], dx[SSDN_MAX_TAPS];   /* forward taps: the conv reads in[y + dy, x + dx] */
+} ssdn_input_grad_args;
 
 /* Execute `n` ops in order on `stream`.  Returns 0 or a negative error (ssdn_last_error()). */
 int ssdn_run_ops(const ssdn_op* ops, int n, void* stream);

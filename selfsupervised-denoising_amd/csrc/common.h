@@ -150,6 +150,7 @@ int adam_pack_fusable(const ssdn_adam_args* a, const ssdn_wpack_args* const* ite
 int launch_adam_pack(const ssdn_adam_args* a, const ssdn_wpack_args* const* items, int n, hipStream_t s);
 int launch_metrics(const ssdn_metrics_args* a, hipStream_t s);
 int launch_noise(const ssdn_noise_args* a, hipStream_t s);
+int launch_input_grad(const ssdn_input_grad_args* a, hipStream_t s);   // input_grad.hip
 int conv_lds_bytes(const ssdn_conv_args* a);
 int conv_validate(const ssdn_conv_args* a);                     // conv_mfma.hip: argument checks shared by every conv launcher
 // conv_chain.hip: a run of consecutive main-lane ops on images of <= 64 pixels (3x3 forward layers; data gradients + SSDN_OP_POOL_BWD)

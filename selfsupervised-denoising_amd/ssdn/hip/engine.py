@@ -410,6 +410,16 @@ class DeviceNet:
         if op.type == "grad_pack":
             return op.type, L.GradPackArgs(_ptr(self.t[a["g"]]), self._view(a["dst"]), a["N"], a["C"], a["H"], a["W"], a["cpad"],
                                            _ptr(self.t[P + "gmax"]), _ptr(self.t[P + "scale"]))
+        if op.type == "input_grad":
+            s = L.InputGradArgs()
+            s.g_e0, s.g_d1a = self._view(a["g_e0"]), self._view(a["g_d1a"])
+            s.w_e, s.w_d = self._pp(self._layer(a["layer_e"]).w_off), self._pp(self._layer(a["layer_d"]).w_off)
+            s.out = _ptr(self.t[a["dst"]])
+            s.B, s.C, s.H, s.W, s.R = a["B"], a["C"], a["H"], a["W"], a["R"]
+            s.ntaps = len(a["taps"])
+            for i, (dy, dx) in enumerate(a["taps"]):
+                s.dy[i], s.dx[i] = dy, dx
+            return op.type, s
         raise ValueError("unknown op type " + op.type)
 
 

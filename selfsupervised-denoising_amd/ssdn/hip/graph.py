@@ -301,16 +301,21 @@ class NetPlan:
     cus      compute units of the device (sizes the persistent wgrad grids)
     dev_cus  compute units the LIBRARY sees (ssdn_device_cus: its kernel-selection rules use it); only differs from `cus`
              when a test plans small persistent grids on a big device
+    input_grad  (train plans only) the backward list also computes d/d(network input) into the f32 tensor `dx32` [B,C,H,W]: one
+             SSDN_OP_INPUT_GRAD behind the data gradient that writes g_e0.  False (the default) leaves every tensor and op as it is.
     """
 
     def __init__(self, prefix: str, in_channels: int, out_channels: int, blindspot: bool, B: int, H: int, W: int,
-                 cus: int = 256, train: bool = True, param_base: int = 0, dev_cus: Optional[int] = None):
+                 cus: int = 256, train: bool = True, param_base: int = 0, dev_cus: Optional[int] = None, input_grad: bool = False):
+        if input_grad and not train:
+            raise ValueError("input_grad needs a training plan (train=True)")
         if H % 32 or W % 32:
             raise ValueError("input height/width must be multiples of 32 (NoiseNetwork.input_wh_mul)")
         if blindspot and H != W:
             raise ValueError("blind-spot mode needs square inputs")
         self.prefix, self.C, self.Cout, self.blindspot = prefix, in_channels, out_channels, blindspot
         self.B, self.H, self.W, self.cus, self.train = B, H, W, cus, train
+        self.input_grad = bool(input_grad)
         self.dev_cus = cus if dev_cus is None else dev_cus
         self.R = 4 if blindspot else 1
         self.N = self.R * B
@@ -700,6 +705,12 @@ class NetPlan:
         self._wgrad(L["encode_block_1.2"], View(g_e1), 48, View(e0), 48, 0, None, 0, 48, N, H, W, t3)
         g_e0 = self.grad("g_e0", N, H, W, 48)
         dgrad("encode_block_1.2", g_e1, 48, N, H, W, rt3, 48, View(g_e0), mask=View(e0), mask_sign=signs.get(e0))
+        if self.input_grad:
+            # the network input feeds encode_block_1.0 and the skip half of decode_block_1.0: its gradient gathers both layers'
+            # pre-activation gradients through their input-channel weights and un-rotates (csrc/input_grad.hip)
+            dx32 = self.T("dx32", "f32", (B, C, H, W))
+            b.append(Op("input_grad", dict(g_e0=View(g_e0), g_d1a=View(self.prefix + "g_d1a"), dst=dx32, B=B, C=C, H=H, W=W, R=self.R,
+                                           taps=list(t3), layer_e="encode_block_1.0", layer_d="decode_block_1.0")))
         self._wgrad(L["encode_block_1.0"], View(g_e0), 48, None, 0, 0, View(x16), 16, C, N, H, W, t3)
         if getattr(self, "_mega_ops", None):
             self._plan_mega()

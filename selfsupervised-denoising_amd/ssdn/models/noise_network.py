@@ -3,8 +3,16 @@
 Same constructor, `forward`, `blindspot`, `init_weights`, `input_wh_mul` and `state_dict` layout as the reference module
 (/root/reference/ssdn/ssdn/models/noise_network.py:13-238), but it is NOT a stack of torch.nn layers: the module only
 owns the parameters (as views into one flat fp32 buffer, the layout the fused Adam / RCCL all-reduce work on) and
-`forward` executes the planned op list of `ssdn.hip.graph.NetPlan` through libssdn_hip.so.  There is no eager /
-autograd / CPU fallback: without the HIP library or a GPU `forward` raises.
+`forward` executes the planned op list of `ssdn.hip.graph.NetPlan` through libssdn_hip.so.  There is no eager / CPU
+fallback: without the HIP library or a GPU `forward` raises.
+
+Autograd: when a gradient is wanted (grad mode on, and `x` or any parameter requires grad) `forward` runs a TRAINING plan through
+a torch.autograd.Function; its backward copies dL/d(out) into the plan's upstream-gradient buffer and runs the planned backward list
+-- every weight gradient, plus d/dx (SSDN_OP_INPUT_GRAD) when `x` requires grad.  Parameter gradients come from one fresh copy of a
+module-owned flat gradient buffer, so `.grad` accumulates through torch's AccumulateGrad as for any module.  The plan's activations
+are shared by every grad-mode call of the same input shape: a backward after a second grad-mode forward of that shape raises
+RuntimeError, as does a backward after an in-place parameter update (torch's version check) or a double backward.  Otherwise
+(torch.no_grad(), or nothing requires grad) `forward` runs the forward-only plan and returns a tensor without a graph.
 """
 from __future__ import annotations
 
@@ -15,6 +23,7 @@ from typing import Dict, Optional, Tuple
 import torch
 import torch.nn as nn
 from torch import Tensor
+from torch.autograd.function import once_differentiable
 
 from ssdn.hip.graph import net_layers, net_param_count
 
@@ -35,6 +44,41 @@ class _Slots(nn.Module):
         super().__init__()
         for k, m in children.items():
             self.add_module(k, m)
+
+
+class _NetFunction(torch.autograd.Function):
+    """out = net(x) on a training plan; backward = the plan's backward list (+ SSDN_OP_INPUT_GRAD when x needs a gradient)."""
+
+    @staticmethod
+    def forward(ctx, net: "NoiseNetwork", x: Tensor, *params: Tensor) -> Tensor:
+        slot, out = net._run_grad_forward(x, input_grad=ctx.needs_input_grad[1])
+        ctx.slot, ctx.gen = slot, slot[2]
+        ctx.x_device, ctx.x_dtype = x.device, x.dtype
+        ctx.offsets = [net._param_offset(p) for p in params]
+        ctx.save_for_backward(*params)         # (torch's version check: an in-place update of a parameter before backward raises)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out: Tensor):
+        from ssdn.hip.engine import current_stream
+        params = ctx.saved_tensors
+        eng = ctx.slot[0]
+        if ctx.slot[2] != ctx.gen:
+            raise RuntimeError("NoiseNetwork: the activations of this graph were overwritten by a later grad-mode forward of the same "
+                               "input shape; run backward before the next forward of that shape")
+        eng.tensor("g32").copy_(grad_out.to(dtype=torch.float32))
+        eng.bwd.run(current_stream())
+        dx = None
+        if ctx.needs_input_grad[1]:
+            dx = eng.tensor("dx32").clone().to(device=ctx.x_device, dtype=ctx.x_dtype)
+        grads = [None] * len(params)
+        if any(ctx.needs_input_grad[2:]):
+            flat = eng.grads.clone()           # one copy: the next backward overwrites the engine's buffer
+            for i, (p, off) in enumerate(zip(params, ctx.offsets)):
+                if ctx.needs_input_grad[2 + i]:
+                    grads[i] = flat[off:off + p.numel()].view(p.shape)
+        return (None, dx, *grads)
 
 
 class NoiseNetwork(nn.Module):
@@ -69,7 +113,10 @@ class NoiseNetwork(nn.Module):
             self.add_module(blk, _Slots(blocks[blk]))
         self.output_conv = blocks["output_block"]["4"]          # alias: ONE parameter under two names (noise_network.py:149-156)
         self.output_block = _Slots(blocks["output_block"])
-        self._engines: Dict[Tuple[int, int, int], list] = {}   # shape -> [DeviceNet, parameter version its shadows hold]
+        # (B, H, W) -> [DeviceNet, parameter version its shadows hold] (forward-only plans);
+        # (B, H, W, input_grad) -> [DeviceNet, parameter version, generation] (training plans of the autograd path)
+        self._engines: Dict[tuple, list] = {}
+        self._grad_buf: Optional[Tensor] = None                # flat gradient the training plans' reductions write
         self._version = 0
         self._consume_default_init_draws()
         self.init_weights()
@@ -132,29 +179,58 @@ class NoiseNetwork(nn.Module):
         return r
 
     # ---- execution --------------------------------------------------------------------------------------------
-    def _engine(self, B: int, H: int, W: int):
+    def _engine(self, B: int, H: int, W: int, train: bool = False, input_grad: bool = False):
         from ssdn.hip import lib as L
         from ssdn.hip.engine import DeviceNet
         from ssdn.hip.graph import NetPlan
         if self._flat.device.type != "cuda":
             raise L.SsdnHipError("NoiseNetwork.forward needs an MI355X: parameters live on %s and the ssdn hot path has no CPU "
                                  "fallback" % self._flat.device)
-        key = (B, H, W)
+        key = (B, H, W, bool(input_grad)) if train else (B, H, W)
         if key not in self._engines:
             cus = L.load().ssdn_device_cus()
-            plan = NetPlan("n/", self.in_channels, self.out_channels, self._blindspot, B, H, W, cus=cus, train=False)
-            self._engines[key] = [DeviceNet(plan, self._flat.device, self._flat, None), None]
+            plan = NetPlan("n/", self.in_channels, self.out_channels, self._blindspot, B, H, W, cus=cus, train=train,
+                           input_grad=bool(input_grad))
+            if train and self._grad_buf is None:
+                self._grad_buf = torch.zeros(self.nparams, device=self._flat.device)
+            self._engines[key] = [DeviceNet(plan, self._flat.device, self._flat, self._grad_buf if train else None), None, 0]
             while len(self._engines) > 4:                  # LRU cap: a plan owns all its activation buffers
                 self._engines.pop(next(k for k in self._engines if k != key))
         slot = self._engines.pop(key)
         self._engines[key] = slot
         return slot
 
+    def _param_offset(self, p: Tensor) -> int:
+        """offset (floats) of a parameter inside the flat buffer"""
+        off = (p.data_ptr() - self._flat.data_ptr()) // 4
+        if p.untyped_storage().data_ptr() != self._flat.untyped_storage().data_ptr() or not 0 <= off <= self.nparams - p.numel():
+            raise RuntimeError("NoiseNetwork: a parameter no longer lives in the module's flat buffer")
+        return off
+
+    def _run_grad_forward(self, x: Tensor, input_grad: bool):
+        """forward on the training plan of x's shape (its activations stay for the backward list); -> (engine slot, output)"""
+        from ssdn.hip.engine import current_stream
+        B, _, H, W = x.shape
+        slot = self._engine(B, H, W, train=True, input_grad=input_grad)
+        eng = slot[0]
+        s = current_stream()
+        eng.pack.run(s)                        # (fp16 forward and bf16 data-gradient shadows, as in the forward-only path)
+        slot[1] = (self._version, self._flat._version)
+        slot[2] += 1                           # generation: a graph made by an earlier forward of this engine can no longer backward
+        eng.tensor("in32").copy_(x.to(dtype=torch.float32), non_blocking=True)
+        eng.fwd.run(s)
+        return slot, eng.tensor("out32").clone()
+
     def forward(self, x: Tensor) -> Tensor:
-        """x: float32 [B,C,H,W] (H, W multiples of 32; square when blindspot) -> float32 [B,out_channels,H,W] on the GPU."""
+        """x: float32 [B,C,H,W] (H, W multiples of 32; square when blindspot) -> float32 [B,out_channels,H,W] on the GPU.
+        Differentiable w.r.t. x and the parameters when grad mode is on (module docstring)."""
         from ssdn.hip.engine import current_stream
         if x.dim() != 4 or x.shape[1] != self.in_channels:
             raise ValueError("expected input [B,%d,H,W], got %s" % (self.in_channels, tuple(x.shape)))
+        if torch.is_grad_enabled():
+            params = list(self.parameters())
+            if x.requires_grad or any(p.requires_grad for p in params):
+                return _NetFunction.apply(self, x, *params)
         B, _, H, W = x.shape
         slot = self._engine(B, H, W)
         eng = slot[0]
