@@ -35,7 +35,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SSDN_ABI_VERSION 15
+#define SSDN_ABI_VERSION 16
 #define SSDN_MAX_TAPS 9
 
 /* NHWC fp16 view: element (n,y,x,c) lives at p[((n*H + y)*W + x)*cs + co + c]. */
@@ -68,7 +68,9 @@ enum ssdn_op_type {
     SSDN_OP_EVENT_RECORD = 20, /* hipEventRecord(event) on the op's lane: lets a consumer outside the list (the gradient
                                   all-reduce on its own stream) wait for a PREFIX of the list */
     SSDN_OP_NOISE = 21,        /* training patch stream: uint8 clean patches -> noisy / clean / reference fp32 (+ Noise2Void) */
-    SSDN_OP_INPUT_GRAD = 22    /* gradient w.r.t. the network input (NoiseNetwork under autograd with x.requires_grad) */
+    SSDN_OP_INPUT_GRAD = 22,   /* gradient w.r.t. the network input (NoiseNetwork under autograd with x.requires_grad) */
+    SSDN_OP_HEAD_VJP = 23,     /* vector-Jacobian product of the SSDN head: any upstream gradient of LOSS / posterior mean / mu */
+    SSDN_OP_MSE_VJP = 24       /* the same for the (masked) MSE pipelines: LOSS / network output */
 };
 
 /* One record of the op list.  `args` points at the matching ssdn_*_args struct (host memory).
@@ -377,6 +379,52 @@ typedef struct ssdn_mse_args {
     float* g;
     uint32_t* gmax;
 } ssdn_mse_args;
+
+/* ---- SSDN_OP_HEAD_VJP / SSDN_OP_MSE_VJP ----------------------------------------------------------
+ * replaces: autograd's backward through Denoiser._ssdn_pipeline / _mse_pipeline / _mask_mse_pipeline (denoiser.py:140-397) for ANY
+ * upstream gradient of the pipeline's differentiable outputs, not just d mean(LOSS) (Denoiser.run_pipeline under autograd).
+ * Upstream gradients (any may be NULL = no gradient for that output): w[b] = dL/dLOSS[b]; g_pme = dL/dIMG_DENOISED [B,C,H,W];
+ * g_mu = dL/dIMG_MU [B,C,H,W] (ssdn only).  HEAD_VJP writes g_net_out = dL/dnet_out [B,Cout,H,W], the per-workgroup partials
+ * partial[b][chunk][1] of dL/dest_raw (same layout / chunking as SSDN_OP_HEAD_SSDN; partial[..][0], the loss sums, are left alone),
+ * then reduces them in HEAD_FINAL's order into g_est (const: [1], var: [B]) and, for var, g_sigma_out = g_est[b]/(H*W).
+ * MSE_VJP writes g = w[b] dLOSS[b]/dout + g_pme (masked: the coordinates of batch element 0, duplicates counted, as SSDN_OP_MASK_MSE).
+ * |g| is folded into gmax (gmax2: |g_sigma_out|).  Per-pixel math: DESIGN.md section 3.8.
+ * keep = 1 declares that g_net_out / g and the partials still hold what the forward's loss op wrote (d mean(LOSS)): then a sample
+ * with no g_pme / g_mu and w[b] == 1.f/B exactly keeps them untouched (the check runs on the device), so mean(LOSS) under autograd
+ * is bit-identical to the planned backward pass at every batch size.  Every reduction is in a fixed order: bit-reproducible. */
+typedef struct ssdn_head_vjp_args {
+    const float* net_out; /* [B,Cout,H,W] */
+    const float* noisy;   /* [B,C,H,W] */
+    const float* noise_param;
+    const float* est_raw; /* [1] (const) or [B] (var), pre-softplus */
+    int32_t B, C, H, W;
+    int32_t style, mode;
+    const float* w;       /* [B] or NULL */
+    const float* g_pme;   /* [B,C,H,W] or NULL */
+    const float* g_mu;    /* [B,C,H,W] or NULL */
+    int32_t keep;
+    int32_t nchunks;      /* = the forward's */
+    float* g_net_out;
+    float* partial;       /* [B][nchunks][2] */
+    uint32_t* gmax;
+    float* g_est;         /* const: [1], var: [B], known: NULL */
+    float* g_sigma_out;   /* var: [B,1,H,W] */
+    uint32_t* gmax2;      /* var */
+} ssdn_head_vjp_args;
+
+typedef struct ssdn_mse_vjp_args {
+    const float* out;     /* [B,C,H,W] */
+    const float* ref;
+    const int64_t* coords; /* masked: [ncoords][2] (row, col) of batch element 0 */
+    int32_t ncoords;
+    int32_t masked;
+    int32_t B, C, H, W;
+    int32_t keep;
+    const float* w;       /* [B] or NULL */
+    const float* g_pme;   /* [B,C,H,W] or NULL */
+    float* g;             /* [B,C,H,W] */
+    uint32_t* gmax;
+} ssdn_mse_vjp_args;
 
 /* ---- SSDN_OP_ADAM ---------------------------------------------------------------------------
  * replaces: torch.optim.Adam.step over all parameters (train.py:100-107,202): one fused pass over the flat fp32

@@ -144,6 +144,8 @@ int launch_head(const ssdn_head_args* a, hipStream_t s);
 int launch_head_final(const ssdn_head_final_args* a, hipStream_t s);
 int launch_spatial_mean(const ssdn_spatial_mean_args* a, hipStream_t s);
 int launch_mse(const ssdn_mse_args* a, int masked, hipStream_t s);
+int launch_head_vjp(const ssdn_head_vjp_args* a, hipStream_t s);   // head.hip: any upstream gradient of the pipeline outputs
+int launch_mse_vjp(const ssdn_mse_vjp_args* a, hipStream_t s);
 int launch_adam(const ssdn_adam_args* a, hipStream_t s);
 #define ADAM_PACK_MAX 24
 int adam_pack_fusable(const ssdn_adam_args* a, const ssdn_wpack_args* const* items, int n);

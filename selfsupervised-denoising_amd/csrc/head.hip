@@ -449,3 +449,251 @@ int launch_metrics(const ssdn_metrics_args* a, hipStream_t s) {
     hipLaunchKernelGGL(k_metrics, dim3(a->B), dim3(MB), 0, s, *a);
     return 0;
 }
+
+// ---- SSDN_OP_HEAD_VJP / SSDN_OP_MSE_VJP: the pipelines' vector-Jacobian products for any upstream gradient ------------------------
+// (Denoiser.run_pipeline under autograd: dL/dLOSS = w, dL/dIMG_DENOISED = g_pme, dL/dIMG_MU = g_mu; math in DESIGN.md section 3.8.)
+// Same grid and pixel chunking as k_head, so partial[b][chunk][1] lands where the forward put it.  A sample whose request is exactly
+// the forward's d mean(LOSS) (keep, no g_pme / g_mu, w[b] == 1.f/B) returns at once: its gradient and partials stay bit for bit.
+__global__ void k_head_vjp(ssdn_head_vjp_args a) {
+    __shared__ float sh[4];
+    const int b = blockIdx.y;
+    const long long HW = (long long)a.H * a.W;
+    const int C = a.C;
+    const int Cout = C + C * (C + 1) / 2;
+    const float wb = a.w ? a.w[b] : 0.f;
+    if (a.keep && !a.g_pme && !a.g_mu && a.w && wb == 1.f / (float)a.B) return;     // (block-uniform: before any barrier)
+    const float sc = wb / (float)HW;        // LOSS[b] is the mean over the pixels of sample b
+    float est = 0.f, dest_draw = 0.f;
+    if (a.mode != 0) {
+        float raw = a.est_raw[a.mode == 2 ? b : 0];
+        est = softplus_m4(raw);
+        dest_draw = sigmoid_m4(raw);
+    }
+    const float npar = a.noise_param ? a.noise_param[b] : 0.f;
+    const float reg = a.mode != 0 ? 0.1f : 0.f;
+    float gest_acc = 0.f, gabs = 0.f;
+    const long long per = (HW + a.nchunks - 1) / a.nchunks;
+    const long long p0 = (long long)blockIdx.x * per;
+    const long long p1 = p0 + per < HW ? p0 + per : HW;
+    const float* no = a.net_out + (long long)b * Cout * HW;
+    const float* ny = a.noisy + (long long)b * C * HW;
+    const float* gp = a.g_pme ? a.g_pme + (long long)b * C * HW : nullptr;
+    const float* gm = a.g_mu ? a.g_mu + (long long)b * C * HW : nullptr;
+    float* go = a.g_net_out + (long long)b * Cout * HW;
+    for (long long p = p0 + threadIdx.x; p < p1; p += HB) {
+        if (C == 1) {
+            float mu = no[p], av = no[HW + p], y = ny[p];
+            float sig, dsig_dmu = 0.f, dsig_dest = 0.f;
+            if (a.style == 0) {
+                sig = a.mode == 0 ? fmaxf(npar, 1e-3f) : est;
+                dsig_dest = 1.f;
+            } else {
+                float m = fmaxf(mu, 1e-3f);
+                float f = a.mode == 0 ? 1.f / npar : est;
+                sig = sqrtf(m * f);
+                dsig_dmu = mu > 1e-3f ? 0.5f * f / sig : 0.f;
+                dsig_dest = 0.5f * m / sig;
+            }
+            float sx = av * av, sn = sig * sig, sy = sx + sn;
+            float d = y - mu;
+            float dmu = 0.f, dsx = 0.f, dsn = 0.f, dsig = 0.f;
+            if (sc != 0.f) {            // LOSS: l = d^2/sy + log sy (- 0.1 sig)
+                float dsy = (-d * d / (sy * sy) + 1.f / sy) * sc;
+                dmu = -2.f * d / sy * sc;
+                dsx = dsy;
+                dsn = dsy;
+                dsig = -reg * sc;
+            }
+            if (gp) {                   // posterior mean (y sx + mu sn) / sy
+                float g = gp[p], rs = 1.f / sy;
+                float t = g * d * rs * rs;
+                dmu += g * sn * rs;
+                dsx += sn * t;
+                dsn -= sx * t;
+            }
+            dsig += 2.f * sig * dsn;
+            float gmu = dmu + dsig * dsig_dmu + (gm ? gm[p] : 0.f);
+            float ga = 2.f * av * dsx;
+            go[p] = gmu;
+            go[HW + p] = ga;
+            gabs = fmaxf(gabs, fmaxf(fabsf(gmu), fabsf(ga)));
+            gest_acc += dsig * dsig_dest;
+        } else {
+            float mu[3], A[6], y[3], sig[3], dsig_dmu[3], dsig_dest[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { mu[c] = no[c * HW + p]; y[c] = ny[c * HW + p]; }
+#pragma unroll
+            for (int c = 0; c < 6; ++c) A[c] = no[(3 + c) * HW + p];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (a.style == 0) {
+                    sig[c] = a.mode == 0 ? fmaxf(npar, 1e-3f) : est;
+                    dsig_dmu[c] = 0.f;
+                    dsig_dest[c] = 1.f;
+                } else {
+                    float m = fmaxf(mu[c], 1e-3f);
+                    float f = a.mode == 0 ? 1.f / npar : est;
+                    sig[c] = sqrtf(m * f);
+                    dsig_dmu[c] = mu[c] > 1e-3f ? 0.5f * f / sig[c] : 0.f;
+                    dsig_dest[c] = 0.5f * m / sig[c];
+                }
+            }
+            float x00 = A[0] * A[0] + A[1] * A[1] + A[2] * A[2];
+            float x01 = A[1] * A[3] + A[2] * A[4];
+            float x02 = A[2] * A[5];
+            float x11 = A[3] * A[3] + A[4] * A[4];
+            float x12 = A[4] * A[5];
+            float x22 = A[5] * A[5];
+            float n0 = sig[0] * sig[0], n1 = sig[1] * sig[1], n2 = sig[2] * sig[2];
+            float s00 = x00 + n0, s01 = x01, s02 = x02, s11 = x11 + n1, s12 = x12, s22 = x22 + n2;
+            float d0 = y[0] - mu[0], d1 = y[1] - mu[1], d2 = y[2] - mu[2];
+            // G: dL/dSigma_x as a symmetric matrix (dL/dx01 as a scalar = 2 G01, the convention of k_head's G U map);
+            // dn: dL/d(sigma_c^2); gmu: dL/dmu without the sigma chain
+            float g00 = 0.f, g01 = 0.f, g02 = 0.f, g11 = 0.f, g12 = 0.f, g22 = 0.f;
+            float dn0 = 0.f, dn1 = 0.f, dn2 = 0.f, gmu0 = 0.f, gmu1 = 0.f, gmu2 = 0.f, rg = 0.f;
+            if (sc != 0.f) {            // LOSS: 1/2 log det Sy + 1/2 d^T Sy^-1 d (- 0.1 mean sig); G = 1/2 Sy^-1 [det>0] - 1/2 q q^T
+                float c00 = s11 * s22 - s12 * s12, c01 = s02 * s12 - s01 * s22, c02 = s01 * s12 - s02 * s11;
+                float c11 = s00 * s22 - s02 * s02, c12 = s01 * s02 - s00 * s12, c22 = s00 * s11 - s01 * s01;
+                float det = s00 * c00 + s01 * c01 + s02 * c02;
+                float rdet = 1.f / det;
+                float i00 = c00 * rdet, i01 = c01 * rdet, i02 = c02 * rdet, i11 = c11 * rdet, i12 = c12 * rdet, i22 = c22 * rdet;
+                float q0 = i00 * d0 + i01 * d1 + i02 * d2;
+                float q1 = i01 * d0 + i11 * d1 + i12 * d2;
+                float q2 = i02 * d0 + i12 * d1 + i22 * d2;
+                float hd = det > 0.f ? 0.5f : 0.f;
+                g00 = (hd * i00 - 0.5f * q0 * q0) * sc; g01 = (hd * i01 - 0.5f * q0 * q1) * sc; g02 = (hd * i02 - 0.5f * q0 * q2) * sc;
+                g11 = (hd * i11 - 0.5f * q1 * q1) * sc; g12 = (hd * i12 - 0.5f * q1 * q2) * sc; g22 = (hd * i22 - 0.5f * q2 * q2) * sc;
+                dn0 = g00; dn1 = g11; dn2 = g22;
+                gmu0 = -q0 * sc; gmu1 = -q1 * sc; gmu2 = -q2 * sc;
+                rg = reg * (1.f / 3.f) * sc;
+            }
+            if (gp) {                   // posterior mean mu + S' T^-1 d, S' = Sx + eps I, T = Sy + 2 eps I (the forward's form)
+                const float e = 1e-6f;
+                float ga0 = gp[p], ga1 = gp[HW + p], ga2 = gp[2 * HW + p];
+                float t00 = s00 + 2 * e, t11 = s11 + 2 * e, t22 = s22 + 2 * e;
+                float k00 = t11 * t22 - s12 * s12, k01 = s02 * s12 - s01 * t22, k02 = s01 * s12 - s02 * t11;
+                float k11 = t00 * t22 - s02 * s02, k12 = s01 * s02 - t00 * s12, k22 = t00 * t11 - s01 * s01;
+                float rd = 1.f / (t00 * k00 + s01 * k01 + s02 * k02);
+                float r0 = (k00 * d0 + k01 * d1 + k02 * d2) * rd;
+                float r1 = (k01 * d0 + k11 * d1 + k12 * d2) * rd;
+                float r2 = (k02 * d0 + k12 * d1 + k22 * d2) * rd;
+                float u0 = (x00 + e) * ga0 + x01 * ga1 + x02 * ga2;       // S' g
+                float u1 = x01 * ga0 + (x11 + e) * ga1 + x12 * ga2;
+                float u2 = x02 * ga0 + x12 * ga1 + (x22 + e) * ga2;
+                float h0 = (k00 * u0 + k01 * u1 + k02 * u2) * rd;        // h = T^-1 S' g
+                float h1 = (k01 * u0 + k11 * u1 + k12 * u2) * rd;
+                float h2 = (k02 * u0 + k12 * u1 + k22 * u2) * rd;
+                float e0 = ga0 - h0, e1 = ga1 - h1, e2 = ga2 - h2;
+                gmu0 += e0; gmu1 += e1; gmu2 += e2;
+                g00 += e0 * r0; g11 += e1 * r1; g22 += e2 * r2;          // (g - h) r^T, symmetrised
+                g01 += 0.5f * (e0 * r1 + e1 * r0);
+                g02 += 0.5f * (e0 * r2 + e2 * r0);
+                g12 += 0.5f * (e1 * r2 + e2 * r1);
+                dn0 -= h0 * r0; dn1 -= h1 * r1; dn2 -= h2 * r2;
+            }
+            float ds0 = 2.f * sig[0] * dn0 - rg, ds1 = 2.f * sig[1] * dn1 - rg, ds2 = 2.f * sig[2] * dn2 - rg;
+            float g[9];
+            g[0] = gmu0 + ds0 * dsig_dmu[0] + (gm ? gm[p] : 0.f);
+            g[1] = gmu1 + ds1 * dsig_dmu[1] + (gm ? gm[HW + p] : 0.f);
+            g[2] = gmu2 + ds2 * dsig_dmu[2] + (gm ? gm[2 * HW + p] : 0.f);
+            g[3] = 2.f * (g00 * A[0]);
+            g[4] = 2.f * (g00 * A[1] + g01 * A[3]);
+            g[5] = 2.f * (g00 * A[2] + g01 * A[4] + g02 * A[5]);
+            g[6] = 2.f * (g01 * A[1] + g11 * A[3]);
+            g[7] = 2.f * (g01 * A[2] + g11 * A[4] + g12 * A[5]);
+            g[8] = 2.f * (g02 * A[2] + g12 * A[4] + g22 * A[5]);
+#pragma unroll
+            for (int c = 0; c < 9; ++c) {
+                go[c * HW + p] = g[c];
+                gabs = fmaxf(gabs, fabsf(g[c]));
+            }
+            gest_acc += ds0 * dsig_dest[0] + ds1 * dsig_dest[1] + ds2 * dsig_dest[2];
+        }
+    }
+    float gs = block_sum(gest_acc, sh);
+    if (threadIdx.x == 0) a.partial[((long long)b * a.nchunks + blockIdx.x) * 2 + 1] = gs * dest_draw;
+    if (a.gmax) atomic_max_abs_block(a.gmax, gabs, sh);
+}
+// g_est from the partials in k_head_final's order (skipped samples' partials are the forward's: the sum is too); the loss sums untouched
+__global__ void k_head_vjp_final(ssdn_head_vjp_args a) {
+    int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < a.B && a.mode == 2) {
+        float g = 0.f;
+        for (int c = 0; c < a.nchunks; ++c) g += a.partial[((long long)b * a.nchunks + c) * 2 + 1];
+        a.g_est[b] = g;
+    }
+    if (a.mode == 1 && b == 0) {
+        float g = 0.f;
+        for (int bb = 0; bb < a.B; ++bb)
+            for (int c = 0; c < a.nchunks; ++c) g += a.partial[((long long)bb * a.nchunks + c) * 2 + 1];
+        a.g_est[0] = g;
+    }
+}
+int launch_head_vjp(const ssdn_head_vjp_args* a, hipStream_t s) {
+    if (a->C != 1 && a->C != 3) return ssdn_set_error("head_vjp: C must be 1 or 3");
+    if (a->B < 1 || a->H < 1 || a->W < 1 || a->nchunks < 1) return ssdn_set_error("head_vjp: bad shape");
+    if (a->mode < 0 || a->mode > 2 || a->style < 0 || a->style > 1) return ssdn_set_error("head_vjp: bad style / mode");
+    if (!a->net_out || !a->noisy || !a->g_net_out || !a->partial) return ssdn_set_error("head_vjp: net_out, noisy, g_net_out and partial must be given");
+    if (a->mode == 0 && !a->noise_param) return ssdn_set_error("head_vjp: mode known needs noise_param");
+    if (a->mode != 0 && !a->est_raw) return ssdn_set_error("head_vjp: modes const / var need est_raw");
+    hipLaunchKernelGGL(k_head_vjp, dim3(a->nchunks, a->B), dim3(HB), 0, s, *a);
+    if (a->mode != 0 && a->g_est) {
+        hipLaunchKernelGGL(k_head_vjp_final, dim3((a->B + 63) / 64), dim3(64), 0, s, *a);
+        if (a->mode == 2 && a->g_sigma_out) {
+            ssdn_head_final_args f = {a->partial, a->B, a->nchunks, a->H, a->W, a->mode, nullptr, a->g_est, a->g_sigma_out, a->gmax2};
+            long long n = (long long)a->B * a->H * a->W;
+            hipLaunchKernelGGL(k_fill_sigma_grad, dim3((int)((n + 255) / 256)), dim3(256), 0, s, f);
+        }
+    }
+    return 0;
+}
+
+// g = w[b] dLOSS[b]/dout + g_pme, one block per sample.  MSE: LOSS[b] = mean_chw (out - ref)^2.  Masked: g_pme everywhere, then the
+// loss term added at element 0's coordinates, channel-sequential over the coordinates as in k_mask_mse (duplicates count twice).
+__global__ void k_mse_vjp(ssdn_mse_vjp_args a) {
+    __shared__ float sh[4];
+    const int b = blockIdx.x;
+    const long long HW = (long long)a.H * a.W;
+    const long long n = (long long)a.C * HW;
+    const float wb = a.w ? a.w[b] : 0.f;
+    if (a.keep && !a.g_pme && a.w && wb == 1.f / (float)a.B) return;             // (block-uniform: before any barrier)
+    float* g = a.g + b * n;
+    const float* gp = a.g_pme ? a.g_pme + b * n : nullptr;
+    const float* out = a.out + b * n;
+    const float* ref = a.ref ? a.ref + b * n : nullptr;
+    const bool lossg = a.w && ref;
+    float gabs = 0.f;
+    if (!a.masked) {
+        const float k = wb * (2.f / (float)n);
+        for (long long i = threadIdx.x; i < n; i += HB) {
+            float v = lossg ? k * (out[i] - ref[i]) : 0.f;
+            if (gp) v += gp[i];
+            g[i] = v;
+            gabs = fmaxf(gabs, fabsf(v));
+        }
+    } else {
+        for (long long i = threadIdx.x; i < n; i += HB) g[i] = gp ? gp[i] : 0.f;
+        __syncthreads();
+        if (lossg && a.coords) {
+            const float k = wb * (2.f / (float)a.C);
+            for (int c = threadIdx.x; c < a.C; c += HB)
+                for (int q = 0; q < a.ncoords; ++q) {
+                    long long r = a.coords[2 * q], cc = a.coords[2 * q + 1];
+                    if (r < 0 || r >= a.H || cc < 0 || cc >= a.W) continue;
+                    long long off = c * HW + r * a.W + cc;
+                    g[off] += k * (out[off] - ref[off]);
+                }
+        }
+        __syncthreads();
+        for (long long i = threadIdx.x; i < n; i += HB) gabs = fmaxf(gabs, fabsf(g[i]));
+    }
+    if (a.gmax) atomic_max_abs_block(a.gmax, gabs, sh);
+}
+int launch_mse_vjp(const ssdn_mse_vjp_args* a, hipStream_t s) {
+    if (a->B < 1 || a->C < 1 || a->H < 1 || a->W < 1) return ssdn_set_error("mse_vjp: bad shape");
+    if (!a->out || !a->g) return ssdn_set_error("mse_vjp: out and g must be given");
+    if (a->w && !a->ref) return ssdn_set_error("mse_vjp: a LOSS gradient needs ref");
+    if (a->w && a->masked && (!a->coords || a->ncoords < 0)) return ssdn_set_error("mse_vjp: masked LOSS gradient needs coords");
+    hipLaunchKernelGGL(k_mse_vjp, dim3(a->B), dim3(HB), 0, s, *a);
+    return 0;
+}

@@ -6,24 +6,33 @@ aliases) and `config_name`.  What differs is everything u
 into ONE flat fp32 device buffer [main net | sigma estimator | learnable sigma scalar]; a forward / loss / backward /
 optimiser step is four calls into libssdn_hip.so (`ssdn.hip.engine.DenoiserEngine`); nn.DataParallel is gone -- data
 parallelism is one process per GPU with an RCCL all-reduce of the flat gradient (`ssdn.hip.dp`).
+
+Autograd: a training-mode `run_pipeline` / `forward` with grad enabled returns LOSS, IMG_DENOISED and IMG_MU (MSE pipelines: LOSS when
+there is a reference, and IMG_DENOISED) as outputs of one autograd node.  Its backward takes ANY upstream gradient of them -- per-sample
+weights or other reductions of LOSS, a loss on the posterior mean or on mu, or several at once -- copies those that arrived into the
+engine and runs the vector-Jacobian product of the loss head on the GPU (SSDN_OP_HEAD_VJP / SSDN_OP_MSE_VJP), then the planned
+backward pass.  `torch.mean(LOSS).backward()` gives exactly the gradient of `Denoiser.backward()`.  As before, the parameters' `.grad`
+are views of the flat gradient buffer: every backward OVERWRITES them (no accumulation), so all terms of a loss must go through ONE
+`backward()` call.  A graph whose engine has since run another training forward (`run_pipeline` or `train_step` of the same shape)
+raises RuntimeError on backward.  The planned route `Denoiser.backward()` consumes its forward: afterwards that forward's IMG_DENOISED
+and IMG_MU are plain tensors again (detached in place), as they always were on that route.  NOISE_STD_DEV and MODEL_STD_DEV, eval-mode or no_grad outputs and everything `train_step` returns
+carry no graph; no gradient flows into the noisy input.
 """
 from __future__ import annotations
 
+import weakref
 from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
 from torch import Tensor
+from torch.autograd.function import once_differentiable
 
 import ssdn
 from ssdn.datasets import NoisyDataset
 from ssdn.models import NoiseNetwork
 from ssdn.params import ConfigValue, NoiseValue, Pipeline, PipelineOutput
 
-
-import os as _os
-
-_CHECK_LOSS_GRAD = _os.environ.get("SSDN_CHECK_LOSS_GRAD", "0") == "1"
 _MAX_ENGINES = 4        # cached (batch, size, mode) plans per Denoiser; the least recently used one is dropped beyond this
 
 
@@ -39,28 +48,27 @@ class _ParallelShim(nn.Module):
         return self.module(*a, **k)
 
 
-class _LossBridge(torch.autograd.Function):
-    """Lets the reference's training idiom `torch.mean(outputs[LOSS]).backward()` drive the HIP backward pass:
-    the returned LOSS tensor carries this node; its backward runs the planned backward op list and exposes the flat
-    gradient buffer through every parameter's `.grad`."""
+class _PipelineGrad(torch.autograd.Function):
+    """The differentiable outputs of one training-mode pipeline run (`names`: LOSS / IMG_DENOISED / IMG_MU) as one node.  Its backward
+    hands whichever upstream gradients arrived (None = that output was not used) to the engine that PRODUCED them, which runs the
+    head's vector-Jacobian product and the planned backward lists; the parameters' `.grad` then show the flat gradient buffer."""
 
     @staticmethod
-    def forward(ctx, anchor: Tensor, denoiser: "Denoiser", engine, loss: Tensor):
-        ctx.denoiser, ctx.engine = denoiser, engine        # the engine that PRODUCED this loss, not "the last one used"
-        return loss.clone()
+    def forward(ctx, anchor: Tensor, denoiser: "Denoiser", engine, names: Tuple, *outs: Tensor):
+        ctx.set_materialize_grads(False)
+        ctx.denoiser, ctx.engine, ctx.names, ctx.gen = denoiser, engine, names, engine.gen
+        return tuple(o.clone() for o in outs)
 
     @staticmethod
-    def backward(ctx, grad_out: Tensor):
-        d = ctx.denoiser
-        if grad_out.dim() != 2 or grad_out.shape[1] != 1:
-            raise NotImplementedError("LOSS is [B, 1]; the fused loss head differentiates mean(LOSS) over the batch (train.py:201)")
-        if _CHECK_LOSS_GRAD:      # debug aid (SSDN_CHECK_LOSS_GRAD=1): costs a host-device sync per step
-            B = grad_out.shape[0]
-            if not torch.allclose(grad_out, torch.full_like(grad_out, 1.0 / B), rtol=1e-5, atol=0):
-                raise NotImplementedError("the fused loss head differentiates mean(LOSS) over the batch (train.py:201); "
-                                          "other reductions of LOSS are not supported")
-        d._backward_engine(ctx.engine)
-        return None, None, None, None
+    @once_differentiable
+    def backward(ctx, *grads):
+        eng = ctx.engine
+        if eng.gen != ctx.gen:
+            raise RuntimeError("Denoiser: the buffers of this graph were overwritten by a later training forward (run_pipeline or "
+                               "train_step) of the same input shape; run backward before the next training forward of that shape")
+        g = dict(zip(ctx.names, grads))
+        ctx.denoiser._backward_engine(eng, g.get(PipelineOutput.LOSS), g.get(PipelineOutput.IMG_DENOISED), g.get(PipelineOutput.IMG_MU))
+        return (None, None, None, None) + (None,) * len(grads)
 
 
 class Denoiser(nn.Module):
@@ -110,6 +118,7 @@ class Denoiser(nn.Module):
         self._last_train_engine = None               # engine of the last TRAINING-mode run_pipeline (backward / optimiser)
         self._exchange = None                        # ssdn.hip.dp.GradExchange of train_step (data parallel)
         self._anchor = torch.zeros((), requires_grad=True)
+        self._img_graph = None                       # (engine, generation, weak refs to IMG_DENOISED / IMG_MU) of the last autograd forward
 
     def _add(self, model_id: str, model: nn.Module):
         self._models[model_id] = model
@@ -246,11 +255,21 @@ class Denoiser(nn.Module):
         if train:
             self._last_train_engine = eng
         own = (lambda t: t.clone()) if clone else (lambda t: t)
+        diff = {}
+        if train and bridge:
+            # the differentiable outputs, through one autograd node (which clones them); train_step (bridge=False) has no graph
+            names = ((PipelineOutput.LOSS,) if have_loss else ()) + ((PipelineOutput.IMG_DENOISED, PipelineOutput.IMG_MU)
+                                                                     if self._pipeline == Pipeline.SSDN else (PipelineOutput.IMG_DENOISED,))
+            src = {PipelineOutput.LOSS: eng.loss, PipelineOutput.IMG_MU: eng.mu,
+                   PipelineOutput.IMG_DENOISED: eng.pme if self._pipeline == Pipeline.SSDN else eng.main.tensor("out32")}
+            diff = dict(zip(names, _PipelineGrad.apply(self._anchor, self, eng, names, *[src[n] for n in names])))
+            self._img_graph = (eng, eng.gen, [weakref.ref(diff[n]) for n in names if n != PipelineOutput.LOSS])
+        pick = lambda n, t: diff[n] if n in diff else own(t)   # noqa: E731
         out = {PipelineOutput.INPUTS: data}
         net_out = eng.main.tensor("out32")
         if self._pipeline == Pipeline.SSDN:
-            out[PipelineOutput.IMG_MU] = own(eng.mu)
-            out[PipelineOutput.IMG_DENOISED] = own(eng.pme)
+            out[PipelineOutput.IMG_MU] = pick(PipelineOutput.IMG_MU, eng.mu)
+            out[PipelineOutput.IMG_DENOISED] = pick(PipelineOutput.IMG_DENOISED, eng.pme)
             gauss = eng.style == "gauss"
             nstd = eng.noise_std
             if gauss:
@@ -258,12 +277,10 @@ class Denoiser(nn.Module):
             out[PipelineOutput.NOISE_STD_DEV] = own(nstd)
             out[PipelineOutput.MODEL_STD_DEV] = own(eng.model_std)
         else:
-            out[PipelineOutput.IMG_DENOISED] = own(net_out)
+            out[PipelineOutput.IMG_DENOISED] = pick(PipelineOutput.IMG_DENOISED, net_out)
         if have_loss:
-            loss = eng.loss
-            # (_LossBridge.forward clones; the eval branch clones here)
-            # (train_step drives the backward list itself: no autograd bridge, no copy of the loss)
-            out[PipelineOutput.LOSS] = (_LossBridge.apply(self._anchor, self, eng, loss) if bridge else loss) if train else own(loss)
+            # (train_step drives the backward list itself: no autograd node, no copy of the loss)
+            out[PipelineOutput.LOSS] = pick(PipelineOutput.LOSS, eng.loss)
         return out
 
     def backward(self):
@@ -272,12 +289,25 @@ class Denoiser(nn.Module):
         eng = self._last_train_engine
         if eng is None or not eng.train:
             raise RuntimeError("backward() needs a preceding training-mode run_pipeline()")
-        self._backward_engine(eng)
+        if eng.g_fresh or not eng.loss_fwd:
+            eng.backward()
+        else:       # an autograd backward of this forward has replaced the loss gradient: the VJP of mean(LOSS) restores it
+            eng.vjp_backward(w=torch.full((eng.B,), 1.0 / eng.B, device=self.device))
+        self._expose_grads()
+        # this route consumes the forward: its IMG_DENOISED / IMG_MU leave the graph, as they were before autograd reached them, so code
+        # written for the planned backward (run_pipeline, backward(), then numpy on the images) keeps working
+        g = self._img_graph
+        if g is not None and g[0] is eng and g[1] == eng.gen:
+            for r in g[2]:
+                t = r()
+                if t is not None and t.grad_fn is not None:
+                    t.detach_()
+            self._img_graph = None
 
-    def _backward_engine(self, eng):
+    def _backward_engine(self, eng, w: Optional[Tensor] = None, g_pme: Optional[Tensor] = None, g_mu: Optional[Tensor] = None):
         if eng is None or not eng.train:
-            raise RuntimeError("this LOSS was not produced by a training-mode run_pipeline()")
-        eng.backward()
+            raise RuntimeError("this output was not produced by a training-mode run_pipeline()")
+        eng.vjp_backward(w, g_pme, g_mu)
         self._expose_grads()
 
     def _expose_grads(self):

@@ -501,6 +501,11 @@ class DenoiserEngine:
         self.ops_opt = OpList(opt_recs) if train else None
         self.ops_opt_tail = OpList(self.main.tail_recs + opt_recs) if train and self.main.tail_recs else None
         self._tail_pending = False
+        # autograd route (Denoiser.run_pipeline): generation = training forwards so far (a graph of an older one cannot backward);
+        # g_fresh: g32 / the partials still hold what the forward's loss op wrote (d mean(LOSS)), not a vector-Jacobian product's
+        self.gen = 0
+        self.g_fresh = self.loss_fwd = False
+        self._vjp = None
 
     # ---- op construction -----------------------------------------------------------------------------------
     def _gmax(self, net: Optional[DeviceNet]):
@@ -695,6 +700,9 @@ class DenoiserEngine:
 
     def forward(self, stream=None):
         s = current_stream() if stream is None else stream
+        if self.train:
+            self.gen += 1
+            self.g_fresh = self.loss_fwd = True
         if self.sigma is not None and (int(self.SIGMA_CONCURRENT) & 1):
             ev = self._fork_sigma(s, self.sigma.fwd)
             self.main.fwd.run(s)
@@ -707,6 +715,9 @@ class DenoiserEngine:
 
     def net_forward_only(self, stream=None):
         s = current_stream() if stream is None else stream
+        if self.train:
+            self.gen += 1
+            self.g_fresh = self.loss_fwd = False
         self.main.fwd.run(s)
 
     def backward(self, stream=None, exchange=None, defer_tail=False):
@@ -754,6 +765,62 @@ class DenoiserEngine:
         self.main.bwd.run(s)
         if self.sigma is not None:
             self.sigma.bwd.run(s)
+
+    # ---- autograd: any upstream gradient of the pipeline outputs (SSDN_OP_HEAD_VJP / SSDN_OP_MSE_VJP) -------------------------------
+    def _vjp_setup(self):
+        """the upstream-gradient buffers and the one-op VJP list (built when first needed: eval engines and train_step never pay)"""
+        f32 = dict(dtype=torch.float32, device=self.device)
+        B, Cn, H, W = self.B, self.C, self.H, self.W
+        self.vjp_w = torch.zeros((B,), **f32)
+        self.vjp_g_pme = torch.zeros((B, Cn, H, W), **f32)
+        self.vjp_g_mu = torch.zeros((B, Cn, H, W), **f32) if self.pipeline == "ssdn" else None
+        g32 = _ptr(self.main.tensor("g32"))
+        if self.pipeline == "ssdn":
+            a = L.HeadVjpArgs()
+            a.net_out, a.noisy, a.noise_param = _ptr(self.main.tensor("out32")), _ptr(self.inp), _ptr(self.noise_param)
+            a.B, a.C, a.H, a.W, a.style, a.mode = B, Cn, H, W, STYLE[self.style], MODE[self.mode]
+            a.nchunks, a.g_net_out, a.partial, a.gmax = self.nchunks, g32, _ptr(self.partial), self._gmax(self.main)
+            if self.mode == "const":
+                a.est_raw, a.g_est = _ptr(self.params, 4 * self.est_off), _ptr(self.grads, 4 * self.est_off)
+            elif self.mode == "var":
+                a.est_raw, a.g_est = _ptr(self.est_raw), _ptr(self.g_est_var)
+                a.g_sigma_out, a.gmax2 = _ptr(self.sigma.tensor("g32")), self._gmax(self.sigma)
+            self._vjp = (a, OpList([("head_vjp", a)]))
+        else:
+            a = L.MseVjpArgs(_ptr(self.main.tensor("out32")), _ptr(self.ref), _ptr(self.coords), self.ncoords, int(self.pipeline == "mask_mse"),
+                             B, Cn, H, W, 0, None, None, g32, self._gmax(self.main))
+            self._vjp = (a, OpList([("mse_vjp", a)]))
+
+    def vjp_backward(self, w: Optional[torch.Tensor] = None, g_pme: Optional[torch.Tensor] = None, g_mu: Optional[torch.Tensor] = None,
+                     stream=None):
+        """Backward pass for ANY upstream gradient of the last training forward: w = dL/dLOSS [B] (or [B,1]), g_pme = dL/dIMG_DENOISED,
+        g_mu = dL/dIMG_MU (ssdn), [B,C,H,W]; None = no gradient for that output.  Enqueues the VJP op (the loss gradient g32, the
+        sigma partials and g_est), then the backward lists.  w == 1/B alone (mean(LOSS)) leaves the forward's loss gradient in place
+        (decided on the device): then the result is bit-identical to backward()."""
+        if not self.train:
+            raise L.SsdnHipError("vjp_backward needs a training engine")
+        if self._vjp is None:
+            self._vjp_setup()
+        a, ops = self._vjp
+        a.w = a.g_pme = None
+        if w is not None:
+            self.vjp_w.copy_(w.reshape(self.B), non_blocking=True)
+            a.w = _ptr(self.vjp_w)
+        if g_pme is not None:
+            self.vjp_g_pme.copy_(g_pme, non_blocking=True)
+            a.g_pme = _ptr(self.vjp_g_pme)
+        if self.pipeline == "ssdn":
+            a.g_mu = None
+            if g_mu is not None:
+                self.vjp_g_mu.copy_(g_mu, non_blocking=True)
+                a.g_mu = _ptr(self.vjp_g_mu)
+        elif g_mu is not None:
+            raise L.SsdnHipError("the %s pipeline has no IMG_MU" % self.pipeline)
+        a.keep = int(self.g_fresh)
+        s = current_stream() if stream is None else stream
+        ops.run(s)
+        self.g_fresh = False
+        self.backward(stream=s)
 
     def adam(self, lr: float, step: int, gscale: float = 1.0, stream=None):
         for a in self._adam_args:

@@ -16,7 +16,8 @@ MAX_TAPS = 9
 # op type codes (enum ssdn_op_type)
 OP = dict(pack_input=1, conv=2, pool_fwd=3, pool_bwd=4, upsum_bwd=5, unrot_fwd=6, unrot_bwd=7, wgrad=8, wreduce=9,
           wpack=10, grad_pack=11, head_ssdn=12, head_final=13, spatial_mean=14, mse=15, mask_mse=16, adam=17,
-          metrics=18, zero=19, event_record=20, noise=21, input_grad=22)
+          metrics=18, zero=19, event_record=20, noise=21, input_grad=22, head_vjp=23,
+          mse_vjp=24)
 
 i32, f32, vp = C.c_int32, C.c_float, C.c_void_p
 
@@ -128,14 +129,25 @@ class InputGradArgs(C.Structure):
                 ("R", i32), ("ntaps", i32), ("dy", i32 * MAX_TAPS), ("dx", i32 * MAX_TAPS)]
 
 
+class HeadVjpArgs(C.Structure):
+    _fields_ = [("net_out", vp), ("noisy", vp), ("noise_param", vp), ("est_raw", vp), ("B", i32), ("C", i32), ("H", i32), ("W", i32),
+                ("style", i32), ("mode", i32), ("w", vp), ("g_pme", vp), ("g_mu", vp), ("keep", i32), ("nchunks", i32),
+                ("g_net_out", vp), ("partial", vp), ("gmax", vp), ("g_est", vp), ("g_sigma_out", vp), ("gmax2", vp)]
+
+
+class MseVjpArgs(C.Structure):
+    _fields_ = [("out", vp), ("ref", vp), ("coords", vp), ("ncoords", i32), ("masked", i32), ("B", i32), ("C", i32), ("H", i32),
+                ("W", i32), ("keep", i32), ("w", vp), ("g_pme", vp), ("g", vp), ("gmax", vp)]
+
+
 ARG_TYPES = dict(pack_input=PackInputArgs, conv=ConvArgs, pool_fwd=PoolArgs, pool_bwd=PoolArgs, upsum_bwd=UpsumArgs,
                  unrot_fwd=UnrotArgs, unrot_bwd=UnrotArgs, wgrad=WgradArgs, wreduce=WreduceArgs, wpack=WpackArgs,
                  grad_pack=GradPackArgs, head_ssdn=HeadArgs, head_final=HeadFinalArgs, spatial_mean=SpatialMeanArgs,
                  mse=MseArgs, mask_mse=MseArgs, adam=AdamArgs, metrics=MetricsArgs, zero=ZeroArgs, event_record=EventArgs, noise=NoiseArgs,
-                 input_grad=InputGradArgs)
+                 input_grad=InputGradArgs, head_vjp=HeadVjpArgs, mse_vjp=MseVjpArgs)
 
 # every symbol include/ssdn_hip.h declares
-ABI_VERSION = 15      # SSDN_ABI_VERSION of include/ssdn_hip.h this binding mirrors
+ABI_VERSION = 16      # SSDN_ABI_VERSION of include/ssdn_hip.h this binding mirrors
 
 SYMBOLS = ["ssdn_run_ops", "ssdn_stream_order", "ssdn_conv_lds_bytes", "ssdn_wgrad_lds_bytes", "ssdn_abi_version", "ssdn_last_error",
            "ssdn_device_cus", "ssdn_probe_mfma", "ssdn_probe_tr16", "ssdn_struct_size", "ssdn_profile_enable",
