@@ -35,7 +35,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SSDN_ABI_VERSION 16
+#define SSDN_ABI_VERSION 17
 #define SSDN_MAX_TAPS 9
 
 /* NHWC fp16 view: element (n,y,x,c) lives at p[((n*H + y)*W + x)*cs + co + c]. */
@@ -391,7 +391,9 @@ typedef struct ssdn_mse_args {
  * |g| is folded into gmax (gmax2: |g_sigma_out|).  Per-pixel math: DESIGN.md section 3.8.
  * keep = 1 declares that g_net_out / g and the partials still hold what the forward's loss op wrote (d mean(LOSS)): then a sample
  * with no g_pme / g_mu and w[b] == 1.f/B exactly keeps them untouched (the check runs on the device), so mean(LOSS) under autograd
- * is bit-identical to the planned backward pass at every batch size.  Every reduction is in a fixed order: bit-reproducible. */
+ * is bit-identical to the planned backward pass at every batch size.  Every reduction is in a fixed order: bit-reproducible.
+ * g_noisy (ABI 17; NULL = not computed, every other output unchanged bit for bit): HEAD_VJP also writes the head's DIRECT term of
+ * dL/dnoisy [B,C,H,W] -- net_out and sigma held fixed; a sample that keeps g_net_out (keep) still writes it. */
 typedef struct ssdn_head_vjp_args {
     const float* net_out; /* [B,Cout,H,W] */
     const float* noisy;   /* [B,C,H,W] */
@@ -410,6 +412,7 @@ typedef struct ssdn_head_vjp_args {
     float* g_est;         /* const: [1], var: [B], known: NULL */
     float* g_sigma_out;   /* var: [B,1,H,W] */
     uint32_t* gmax2;      /* var */
+    float* g_noisy;       /* [B,C,H,W] or NULL (ABI 17) */
 } ssdn_head_vjp_args;
 
 typedef struct ssdn_mse_vjp_args {
@@ -526,7 +529,9 @@ typedef struct ssdn_noise_args {
  * gradient (the wd shadows of SSDN_OP_WPACK are bf16); accumulation is fp32.  Gather form: every output element is written once by one
  * thread, in a fixed order over (r, t, k) -- bit-reproducible, no atomics, no partial buffers.
  * Requirements: 1 <= C <= 3, R in {1, 4} (4: H == W), H and W multiples of 16, nine taps spanning at most 3 x 3, 16-byte aligned views
- * (cs, co multiples of 8) with 48 / 96 channels. */
+ * (cs, co multiples of 8) with 48 / 96 channels.
+ * add (ABI 17; NULL = none): out = (the sum above) + add, add taken last -- the caller's fixed order of summing several input-gradient
+ * terms.  add may alias out (each element is read once, by the thread that then writes it). */
 typedef struct ssdn_input_grad_args {
     ssdn_view g_e0;      /* bf16 [R*B,H,W,cs] pre-activation gradient of encode_block_1.0 (48 channels) */
     ssdn_view g_d1a;     /* bf16 [R*B,H,W,cs] pre-activation gradient of decode_block_1.0 (96 channels) */
@@ -537,6 +542,7 @@ typedef struct ssdn_input_grad_args {
     int32_t R;           /* 4 (blind-spot) or 1 */
     int32_t ntaps;       /* 9 */
     int32_t dy[SSDN_MAX_TAPS], dx[SSDN_MAX_TAPS];   /* forward taps: the conv reads in[y + dy, x + dx] */
+    const float* add;    /* [B,C,H,W] fp32 or NULL (ABI 17): added last; may alias out */
 } ssdn_input_grad_args;
 
 /* Execute `n` ops in order on `stream`.  Returns 0 or a negative error (ssdn_last_error()). */

@@ -452,16 +452,83 @@ int launch_metrics(const ssdn_metrics_args* a, hipStream_t s) {
 
 // ---- SSDN_OP_HEAD_VJP / SSDN_OP_MSE_VJP: the pipelines' vector-Jacobian products for any upstream gradient ------------------------
 // (Denoiser.run_pipeline under autograd: dL/dLOSS = w, dL/dIMG_DENOISED = g_pme, dL/dIMG_MU = g_mu; math in DESIGN.md section 3.8.)
+// dL/dnoisy of the head at pixel p of one sample, net_out and sigma held fixed.  LOSS: C = 1, l = d^2/sy + log sy:
+// 2 sc d/sy; C = 3, l = 1/2 d^T Sy^-1 d + 1/2 log det Sy: sc Sy^-1 d (Sy as k_head inverts it).  Posterior mean: C = 1, (y sx + mu sn)/sy:
+// g sx/sy; C = 3, mu + S' T^-1 d: h = T^-1 S' g.  IMG_MU does not read the noisy image.
+static __device__ __forceinline__ void head_dy_pixel(const ssdn_head_vjp_args& a, const float* no, const float* ny, const float* gp, float* gy,
+                                                     long long p, long long HW, float sc, float npar, float est) {
+    if (a.C == 1) {
+        float mu = no[p], av = no[HW + p], y = ny[p];
+        float sig;
+        if (a.style == 0) sig = a.mode == 0 ? fmaxf(npar, 1e-3f) : est;
+        else sig = sqrtf(fmaxf(mu, 1e-3f) * (a.mode == 0 ? 1.f / npar : est));
+        float sx = av * av, sy = sx + sig * sig, rs = 1.f / sy, d = y - mu;
+        float v = sc != 0.f ? 2.f * d * rs * sc : 0.f;
+        if (gp) v += gp[p] * sx * rs;
+        gy[p] = v;
+        return;
+    }
+    float A[6], mu[3], n[3];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) A[c] = no[(3 + c) * HW + p];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        mu[c] = no[c * HW + p];
+        float sig;
+        if (a.style == 0) sig = a.mode == 0 ? fmaxf(npar, 1e-3f) : est;
+        else sig = sqrtf(fmaxf(mu[c], 1e-3f) * (a.mode == 0 ? 1.f / npar : est));
+        n[c] = sig * sig;
+    }
+    float x00 = A[0] * A[0] + A[1] * A[1] + A[2] * A[2];
+    float x01 = A[1] * A[3] + A[2] * A[4];
+    float x02 = A[2] * A[5];
+    float x11 = A[3] * A[3] + A[4] * A[4];
+    float x12 = A[4] * A[5];
+    float x22 = A[5] * A[5];
+    float s00 = x00 + n[0], s11 = x11 + n[1], s22 = x22 + n[2];
+    float d0 = ny[p] - mu[0], d1 = ny[HW + p] - mu[1], d2 = ny[2 * HW + p] - mu[2];
+    float v0 = 0.f, v1 = 0.f, v2 = 0.f;
+    if (sc != 0.f) {                    // sc Sy^-1 d (adjugate over determinant, as the forward)
+        float c00 = s11 * s22 - x12 * x12, c01 = x02 * x12 - x01 * s22, c02 = x01 * x12 - x02 * s11;
+        float c11 = s00 * s22 - x02 * x02, c12 = x01 * x02 - s00 * x12, c22 = s00 * s11 - x01 * x01;
+        float rdet = 1.f / (s00 * c00 + x01 * c01 + x02 * c02);
+        v0 = (c00 * d0 + c01 * d1 + c02 * d2) * rdet * sc;
+        v1 = (c01 * d0 + c11 * d1 + c12 * d2) * rdet * sc;
+        v2 = (c02 * d0 + c12 * d1 + c22 * d2) * rdet * sc;
+    }
+    if (gp) {                           // h = T^-1 S' g, S' = Sx + eps I, T = Sy + 2 eps I
+        const float e = 1e-6f;
+        float ga0 = gp[p], ga1 = gp[HW + p], ga2 = gp[2 * HW + p];
+        float t00 = s00 + 2 * e, t11 = s11 + 2 * e, t22 = s22 + 2 * e;
+        float k00 = t11 * t22 - x12 * x12, k01 = x02 * x12 - x01 * t22, k02 = x01 * x12 - x02 * t11;
+        float k11 = t00 * t22 - x02 * x02, k12 = x01 * x02 - t00 * x12, k22 = t00 * t11 - x01 * x01;
+        float rd = 1.f / (t00 * k00 + x01 * k01 + x02 * k02);
+        float u0 = (x00 + e) * ga0 + x01 * ga1 + x02 * ga2;
+        float u1 = x01 * ga0 + (x11 + e) * ga1 + x12 * ga2;
+        float u2 = x02 * ga0 + x12 * ga1 + (x22 + e) * ga2;
+        v0 += (k00 * u0 + k01 * u1 + k02 * u2) * rd;
+        v1 += (k01 * u0 + k11 * u1 + k12 * u2) * rd;
+        v2 += (k02 * u0 + k12 * u1 + k22 * u2) * rd;
+    }
+    gy[p] = v0; gy[HW + p] = v1; gy[2 * HW + p] = v2;
+}
 // Same grid and pixel chunking as k_head, so partial[b][chunk][1] lands where the forward put it.  A sample whose request is exactly
-// the forward's d mean(LOSS) (keep, no g_pme / g_mu, w[b] == 1.f/B) returns at once: its gradient and partials stay bit for bit.
-__global__ void k_head_vjp(ssdn_head_vjp_args a) {
+// the forward's d mean(LOSS) (keep, no g_pme / g_mu, w[b] == 1.f/B) leaves its gradient and partials alone, bit for bit: it returns at
+// once, or, when g_noisy is requested, after writing only that.
+// GY = (a.g_noisy != NULL): the head's direct term of dL/dnoisy in a second pass over the same pixels.  It re-reads
+// its inputs instead of sharing the first pass's values: extra uses of those would let the compiler contract the g_net_out arithmetic
+// differently, and the other outputs must not depend on GY, bit for bit.  The GY = true instance declares its real workgroup size (HB):
+// under the default bound of 1024 threads (128 VGPRs) it spilled to scratch.
+template <bool GY>
+__global__ __attribute__((amdgpu_flat_work_group_size(1, GY ? HB : 1024))) void k_head_vjp(ssdn_head_vjp_args a) {
     __shared__ float sh[4];
     const int b = blockIdx.y;
     const long long HW = (long long)a.H * a.W;
     const int C = a.C;
     const int Cout = C + C * (C + 1) / 2;
     const float wb = a.w ? a.w[b] : 0.f;
-    if (a.keep && !a.g_pme && !a.g_mu && a.w && wb == 1.f / (float)a.B) return;     // (block-uniform: before any barrier)
+    const bool skip = a.keep && !a.g_pme && !a.g_mu && a.w && wb == 1.f / (float)a.B;
+    if (skip && !GY) return;                         // (block-uniform: before any barrier)
     const float sc = wb / (float)HW;        // LOSS[b] is the mean over the pixels of sample b
     float est = 0.f, dest_draw = 0.f;
     if (a.mode != 0) {
@@ -480,7 +547,8 @@ __global__ void k_head_vjp(ssdn_head_vjp_args a) {
     const float* gp = a.g_pme ? a.g_pme + (long long)b * C * HW : nullptr;
     const float* gm = a.g_mu ? a.g_mu + (long long)b * C * HW : nullptr;
     float* go = a.g_net_out + (long long)b * Cout * HW;
-    for (long long p = p0 + threadIdx.x; p < p1; p += HB) {
+    const long long p1v = GY && skip ? p0 : p1;        // (a kept sample: no first pass)
+    for (long long p = p0 + threadIdx.x; p < p1v; p += HB) {
         if (C == 1) {
             float mu = no[p], av = no[HW + p], y = ny[p];
             float sig, dsig_dmu = 0.f, dsig_dest = 0.f;
@@ -610,6 +678,11 @@ __global__ void k_head_vjp(ssdn_head_vjp_args a) {
             gest_acc += ds0 * dsig_dest[0] + ds1 * dsig_dest[1] + ds2 * dsig_dest[2];
         }
     }
+    if constexpr (GY) {
+        float* gy = a.g_noisy + (long long)b * C * HW;
+        for (long long p = p0 + threadIdx.x; p < p1; p += HB) head_dy_pixel(a, no, ny, gp, gy, p, HW, sc, npar, est);
+        if (skip) return;               // (block-uniform: the sample's g_net_out and partials stay the forward's)
+    }
     float gs = block_sum(gest_acc, sh);
     if (threadIdx.x == 0) a.partial[((long long)b * a.nchunks + blockIdx.x) * 2 + 1] = gs * dest_draw;
     if (a.gmax) atomic_max_abs_block(a.gmax, gabs, sh);
@@ -636,7 +709,8 @@ int launch_head_vjp(const ssdn_head_vjp_args* a, hipStream_t s) {
     if (!a->net_out || !a->noisy || !a->g_net_out || !a->partial) return ssdn_set_error("head_vjp: net_out, noisy, g_net_out and partial must be given");
     if (a->mode == 0 && !a->noise_param) return ssdn_set_error("head_vjp: mode known needs noise_param");
     if (a->mode != 0 && !a->est_raw) return ssdn_set_error("head_vjp: modes const / var need est_raw");
-    hipLaunchKernelGGL(k_head_vjp, dim3(a->nchunks, a->B), dim3(HB), 0, s, *a);
+    if (a->g_noisy) hipLaunchKernelGGL(k_head_vjp<true>, dim3(a->nchunks, a->B), dim3(HB), 0, s, *a);
+    else hipLaunchKernelGGL(k_head_vjp<false>, dim3(a->nchunks, a->B), dim3(HB), 0, s, *a);
     if (a->mode != 0 && a->g_est) {
         hipLaunchKernelGGL(k_head_vjp_final, dim3((a->B + 63) / 64), dim3(64), 0, s, *a);
         if (a->mode == 2 && a->g_sigma_out) {

@@ -7,6 +7,7 @@
 //      K-step: 8 channels of one pixel), instead of once per tap.
 //   2. Y goes to LDS; each thread then gathers dx16[p][c] = sum_t Y[p - tap_t][(t,c)] for its own output pixel p = p_r(y,x) and adds it to
 //      its fp32 accumulators -- the rotations meet in registers (fixed order r = 0..R-1, t = 0..8): no atomics, no cross-thread reduction.
+//   3. The optional addend (another input-gradient term of the caller) is added last, per element, by the thread that writes it.
 // The gradient loads of rotation r+1 are issued before the gather of rotation r (register double buffering across the barrier).
 #include "common.h"
 
@@ -117,9 +118,13 @@ __global__ __launch_bounds__(256, 2) void k_input_grad(ssdn_input_grad_args a) {
                 if (c < C) acc[c] += Y[(t * C + c) * IG_NS + s];
         }
     }
+    // (add, optional, comes last: out = S + add.  Each element is read and then written by this one thread, so add may alias out)
 #pragma unroll
     for (int c = 0; c < 3; ++c)
-        if (c < C) a.out[(((long long)b * C + c) * H + y0 + ly) * W + x0 + lx] = acc[c];
+        if (c < C) {
+            const long long off = (((long long)b * C + c) * H + y0 + ly) * W + x0 + lx;
+            a.out[off] = a.add ? acc[c] + a.add[off] : acc[c];
+        }
 }
 
 int launch_input_grad(const ssdn_input_grad_args* a, hipStream_t s) {

@@ -8,15 +8,21 @@ optimiser step is four calls into libssdn_hip.so (`ssdn.hip.engine.DenoiserEngin
 parallelism is one process per GPU with an RCCL all-reduce of the flat gradient (`ssdn.hip.dp`).
 
 Autograd: a training-mode `run_pipeline` / `forward` with grad enabled returns LOSS, IMG_DENOISED and IMG_MU (MSE pipelines: LOSS when
-there is a reference, and IMG_DENOISED) as outputs of one autograd node.  Its backward takes ANY upstream gradient of them -- per-sample
+there is a reference, and IMG_DENOISED) as outputs of one autograd node.  So does a run in ANY mode (eval() included) with grad enabled
+whose noisy input `data[0]` requires grad: the input is then an input of that node too, and its backward returns dL/d(input) -- the
+loss head's direct dependence on the noisy image plus the input gradients of the main network and, for a variable noise level, of the
+sigma estimator, summed on the device in one fixed order -- in the input's dtype and on its device, where torch
+accumulates it into `.grad`.  Such a run uses a training plan with input gradients for that shape; in eval() it does not become the
+forward that `Denoiser.backward()` / `optimizer_step()` act on, and its outputs equal those of the same eval-mode run under no_grad.  Its backward takes ANY upstream gradient of them -- per-sample
 weights or other reductions of LOSS, a loss on the posterior mean or on mu, or several at once -- copies those that arrived into the
 engine and runs the vector-Jacobian product of the loss head on the GPU (SSDN_OP_HEAD_VJP / SSDN_OP_MSE_VJP), then the planned
 backward pass.  `torch.mean(LOSS).backward()` gives exactly the gradient of `Denoiser.backward()`.  As before, the parameters' `.grad`
 are views of the flat gradient buffer: every backward OVERWRITES them (no accumulation), so all terms of a loss must go through ONE
-`backward()` call.  A graph whose engine has since run another training forward (`run_pipeline` or `train_step` of the same shape)
-raises RuntimeError on backward.  The planned route `Denoiser.backward()` consumes its forward: afterwards that forward's IMG_DENOISED
-and IMG_MU are plain tensors again (detached in place), as they always were on that route.  NOISE_STD_DEV and MODEL_STD_DEV, eval-mode or no_grad outputs and everything `train_step` returns
-carry no graph; no gradient flows into the noisy input.
+`backward()` call -- eval-mode input-gradient graphs too.  A graph whose engine has since run another training forward (`run_pipeline`
+or `train_step` of the same shape, or another input-gradient run of that shape) raises RuntimeError on backward.  The planned route `Denoiser.backward()` consumes its forward: afterwards that forward's IMG_DENOISED
+and IMG_MU are plain tensors again (detached in place), as they always were on that route.  NOISE_STD_DEV and MODEL_STD_DEV, no_grad outputs, eval-mode outputs of an input that does not require
+grad and everything `train_step` returns carry no graph (train_step never computes an input gradient).  No gradient flows into the
+reference image, the noise metadata or the std-dev outputs.
 """
 from __future__ import annotations
 
@@ -54,9 +60,11 @@ class _PipelineGrad(torch.autograd.Function):
     head's vector-Jacobian product and the planned backward lists; the parameters' `.grad` then show the flat gradient buffer."""
 
     @staticmethod
-    def forward(ctx, anchor: Tensor, denoiser: "Denoiser", engine, names: Tuple, *outs: Tensor):
+    def forward(ctx, anchor: Tensor, x: Optional[Tensor], denoiser: "Denoiser", engine, names: Tuple, *outs: Tensor):
+        # x: the caller's noisy input when it requires grad (the engine then has input gradients), else None
         ctx.set_materialize_grads(False)
         ctx.denoiser, ctx.engine, ctx.names, ctx.gen = denoiser, engine, names, engine.gen
+        ctx.x_dtype, ctx.x_device = (x.dtype, x.device) if x is not None else (None, None)
         return tuple(o.clone() for o in outs)
 
     @staticmethod
@@ -67,8 +75,11 @@ class _PipelineGrad(torch.autograd.Function):
             raise RuntimeError("Denoiser: the buffers of this graph were overwritten by a later training forward (run_pipeline or "
                                "train_step) of the same input shape; run backward before the next training forward of that shape")
         g = dict(zip(ctx.names, grads))
-        ctx.denoiser._backward_engine(eng, g.get(PipelineOutput.LOSS), g.get(PipelineOutput.IMG_DENOISED), g.get(PipelineOutput.IMG_MU))
-        return (None, None, None, None) + (None,) * len(grads)
+        want_dx = bool(ctx.needs_input_grad[1])
+        ctx.denoiser._backward_engine(eng, g.get(PipelineOutput.LOSS), g.get(PipelineOutput.IMG_DENOISED), g.get(PipelineOutput.IMG_MU),
+                                      want_dx=want_dx)
+        dx = eng.dx.clone().to(device=ctx.x_device, dtype=ctx.x_dtype) if want_dx else None   # (the next backward overwrites eng.dx)
+        return (None, dx, None, None, None) + (None,) * len(grads)
 
 
 class Denoiser(nn.Module):
@@ -164,18 +175,18 @@ class Denoiser(nn.Module):
         return (self._version, self.flat._version)
 
     # ---- engines ---------------------------------------------------------------------------------------------------
-    def _engine(self, B: int, H: int, W: int, train: bool, ncoords: int = 64):
+    def _engine(self, B: int, H: int, W: int, train: bool, ncoords: int = 64, input_grad: bool = False, repack: bool = False):
         from ssdn.hip import lib as L
         from ssdn.hip.engine import DenoiserEngine
         if self.device.type != "cuda":
             raise L.SsdnHipError("Denoiser.run_pipeline needs an MI355X: device is %s and the ssdn hot path has no CPU fallback" % self.device)
-        key = (B, H, W, train, ncoords)
+        key = (B, H, W, train, ncoords) + ((True,) if input_grad else ())        # (input-gradient plans: a key of their own)
         if key not in self._engines:
             cfg = self.cfg
             eng = DenoiserEngine(self._pipeline.value, cfg[ConfigValue.IMAGE_CHANNELS], cfg[ConfigValue.BLINDSPOT],
                                  cfg.get(ConfigValue.NOISE_STYLE) or "gauss", cfg[ConfigValue.NOISE_VALUE].value if self._pipeline == Pipeline.SSDN else "known",
                                  B, H, W, self.device, self.flat, self.flat_grad, self.adam_m, self.adam_v,
-                                 self._n_main, self._n_sig, self._const, train=train, ncoords=ncoords)
+                                 self._n_main, self._n_sig, self._const, train=train, ncoords=ncoords, input_grad=input_grad)
             self._engines[key] = [eng, None]
             while len(self._engines) > _MAX_ENGINES:         # LRU: a plan owns ~1 GB of buffers at BASELINE sizes
                 old = next(k for k in self._engines if k != key)
@@ -186,7 +197,7 @@ class Denoiser(nn.Module):
                     self._last_train_engine = None
         slot = self._engines.pop(key)
         self._engines[key] = slot                            # most recently used last
-        if slot[1] != self._param_version() or not train:
+        if slot[1] != self._param_version() or not train or repack:
             slot[0].repack()
             slot[1] = self._param_version()
         return slot[0]
@@ -224,9 +235,14 @@ class Denoiser(nn.Module):
             if int(c0[:, 0].min()) < -H or int(c0[:, 0].max()) >= H or int(c0[:, 1].min()) < -W or int(c0[:, 1].max()) >= W:
                 raise IndexError("mask coordinates out of range for a %dx%d image" % (H, W))
         train = self.training and torch.is_grad_enabled()
-        eng = self._engine(B, H, W, train, ncoords=(coords.shape[1] if coords is not None else 64))
+        # an input that requires grad (any mode; never train_step): a training plan with input gradients, x an input of the graph.  In
+        # eval() the shadows are re-packed as for every eval-mode run, and the run does not become the last training forward
+        want_x = bridge and torch.is_grad_enabled() and inp.requires_grad
+        eng = self._engine(B, H, W, train or want_x, ncoords=(coords.shape[1] if coords is not None else 64), input_grad=want_x,
+                           repack=want_x and not train)
         if inp.data_ptr() != eng.inp.data_ptr():                          # (a producer may have written the engine's buffer itself)
-            eng.inp.copy_(inp.to(torch.float32), non_blocking=True)      # device boundary (denoiser.py:143,186)
+            # detached: the engine's persistent buffer (input_buffer(), the sigma network's input) never joins the caller's graph
+            eng.inp.copy_(inp.detach().to(torch.float32), non_blocking=True)      # device boundary (denoiser.py:143,186)
         have_loss = True
         if self._pipeline == Pipeline.SSDN:
             if self.cfg[ConfigValue.NOISE_VALUE] == NoiseValue.KNOWN:
@@ -256,14 +272,15 @@ class Denoiser(nn.Module):
             self._last_train_engine = eng
         own = (lambda t: t.clone()) if clone else (lambda t: t)
         diff = {}
-        if train and bridge:
+        if (train and bridge) or want_x:
             # the differentiable outputs, through one autograd node (which clones them); train_step (bridge=False) has no graph
             names = ((PipelineOutput.LOSS,) if have_loss else ()) + ((PipelineOutput.IMG_DENOISED, PipelineOutput.IMG_MU)
                                                                      if self._pipeline == Pipeline.SSDN else (PipelineOutput.IMG_DENOISED,))
             src = {PipelineOutput.LOSS: eng.loss, PipelineOutput.IMG_MU: eng.mu,
                    PipelineOutput.IMG_DENOISED: eng.pme if self._pipeline == Pipeline.SSDN else eng.main.tensor("out32")}
-            diff = dict(zip(names, _PipelineGrad.apply(self._anchor, self, eng, names, *[src[n] for n in names])))
-            self._img_graph = (eng, eng.gen, [weakref.ref(diff[n]) for n in names if n != PipelineOutput.LOSS])
+            diff = dict(zip(names, _PipelineGrad.apply(self._anchor, inp if want_x else None, self, eng, names, *[src[n] for n in names])))
+            if train:                    # (what Denoiser.backward() consumes: the last TRAINING forward's images)
+                self._img_graph = (eng, eng.gen, [weakref.ref(diff[n]) for n in names if n != PipelineOutput.LOSS])
         pick = lambda n, t: diff[n] if n in diff else own(t)   # noqa: E731
         out = {PipelineOutput.INPUTS: data}
         net_out = eng.main.tensor("out32")
@@ -304,10 +321,11 @@ class Denoiser(nn.Module):
                     t.detach_()
             self._img_graph = None
 
-    def _backward_engine(self, eng, w: Optional[Tensor] = None, g_pme: Optional[Tensor] = None, g_mu: Optional[Tensor] = None):
+    def _backward_engine(self, eng, w: Optional[Tensor] = None, g_pme: Optional[Tensor] = None, g_mu: Optional[Tensor] = None,
+                         want_dx: bool = False):
         if eng is None or not eng.train:
             raise RuntimeError("this output was not produced by a training-mode run_pipeline()")
-        eng.vjp_backward(w, g_pme, g_mu)
+        eng.vjp_backward(w, g_pme, g_mu, want_dx=want_dx)
         self._expose_grads()
 
     def _expose_grads(self):

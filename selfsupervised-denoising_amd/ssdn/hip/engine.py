@@ -60,7 +60,7 @@ class DeviceNet:
           "u32": torch.int32, "i64": torch.int64, "u8": torch.uint8}
 
     def __init__(self, plan: NetPlan, device, params: torch.Tensor, grads: Optional[torch.Tensor],
-                 shared: Optional[Dict[str, torch.Tensor]] = None):
+                 shared: Optional[Dict[str, torch.Tensor]] = None, hold_input_grad: bool = False):
         self.plan, self.device = plan, device
         self.params, self.grads = params, grads
         self.t: Dict[str, torch.Tensor] = dict(shared or {})
@@ -72,6 +72,15 @@ class DeviceNet:
             self.t[name] = torch.zeros(spec.shape, dtype=self.DT[spec.kind], device=device)
         self.fwd = OpList([self._mat(op) for op in plan.fwd])
         self._bwd_recs, self._bwd_layers = self._group_reductions(plan, [self._mat(op) for op in plan.bwd])
+        # the SSDN_OP_INPUT_GRAD record of an input-gradient plan (its owner may set the addend); hold_input_grad: the op leaves the
+        # backward list and runs as `input_grad_ops` where the owner enqueues it (behind a term computed on another stream)
+        k = next((i for i, r in enumerate(self._bwd_recs) if r[0] == "input_grad"), None)
+        self.input_grad_args = self._bwd_recs[k][1] if k is not None else None
+        self.input_grad_ops = None
+        if hold_input_grad and k is not None:
+            self.input_grad_ops = OpList([self._bwd_recs[k][:2]])
+            del self._bwd_recs[k]
+            del self._bwd_layers[k]
         self.bwd = OpList(self._bwd_recs, lanes=True)
         # the last gradient bucket's slab reductions close the list: a training step may run them in front of its optimiser launch
         # instead (DeviceEngine.backward(defer_tail=True)): [weight-gradient lane: wait for the main lane's last launch, two
@@ -457,8 +466,11 @@ class DenoiserEngine:
 
     def __init__(self, pipeline: str, channels: int, blindspot: bool, style: str, mode: str, B: int, H: int, W: int,
                  device, params: torch.Tensor, grads: torch.Tensor, adam_m: torch.Tensor, adam_v: torch.Tensor,
-                 n_main: int, n_sigma: int, has_est: bool, train: bool = True, ncoords: int = 64):
+                 n_main: int, n_sigma: int, has_est: bool, train: bool = True, ncoords: int = 64, input_grad: bool = False):
+        if input_grad and not train:
+            raise ValueError("input_grad needs a training engine (train=True)")
         self.pipeline, self.C, self.blindspot, self.mode = pipeline, channels, blindspot, mode
+        self.input_grad = bool(input_grad)
         self.style = "poisson" if style.startswith("poisson") else "gauss"
         self.B, self.H, self.W, self.device, self.train = B, H, W, device, train
         self.params, self.grads, self.m, self.v = params, grads, adam_m, adam_v
@@ -469,12 +481,26 @@ class DenoiserEngine:
         cout = channels + channels * (channels + 1) // 2 if pipeline == "ssdn" else channels
         f32 = dict(dtype=torch.float32, device=device)
         self.inp = torch.zeros((B, channels, H, W), **f32)
-        self.main = DeviceNet(NetPlan("m/", channels, cout, blindspot, B, H, W, cus=cus, train=train, param_base=0),
-                              device, params, grads, shared={"m/in32": self.inp})
+        var = pipeline == "ssdn" and mode == "var"
+        self.main = DeviceNet(NetPlan("m/", channels, cout, blindspot, B, H, W, cus=cus, train=train, param_base=0, input_grad=self.input_grad),
+                              device, params, grads, shared={"m/in32": self.inp}, hold_input_grad=self.input_grad and var)
         self.sigma = None
-        if pipeline == "ssdn" and mode == "var":
-            self.sigma = DeviceNet(NetPlan("s/", channels, 1, False, B, H, W, cus=cus, train=train, param_base=n_main),
+        if var:
+            self.sigma = DeviceNet(NetPlan("s/", channels, 1, False, B, H, W, cus=cus, train=train, param_base=n_main, input_grad=self.input_grad),
                                    device, params, grads, shared={"s/in32": self.inp})
+        # dL/d(noisy input) of the autograd route (vjp_backward(want_dx=True)), summed on the device in ONE fixed order:
+        #   dx = S_main + (S_sigma + head)
+        # head: the loss head's direct term (SSDN_OP_HEAD_VJP's g_noisy, written first); S_sigma / S_main: the two networks'
+        # SSDN_OP_INPUT_GRAD sums, each adding the term before it last.  The main network's op writes `dx` in place (add = out = dx)
+        # inside its backward list; in mode var the sigma network's runs on the side stream into its own dx32 (add = dx) and the main
+        # network's is held out of its list and enqueued behind the join (add = the sigma network's dx32).  MSE pipelines: dx = S_main.
+        # (a backward pass without the head term -- Denoiser.backward(), vjp_backward without want_dx -- leaves the head's addend off:
+        #  `dx` then holds the networks' terms only, and never accumulates across passes)
+        self.dx = None
+        if self.input_grad:
+            self.dx = self.main.tensor("dx32")
+            if self.sigma is not None:
+                self.main.input_grad_args.add = _ptr(self.sigma.tensor("dx32"))
         self.est_off = n_main + n_sigma if has_est else None
         # loss-side buffers
         self.loss = torch.zeros((B, 1), **f32)
@@ -593,6 +619,8 @@ class DenoiserEngine:
         """The op lists of this engine with every pointer replaced by (tensor, offset), the tensor table, and a JSON description.
         ssdn_plan_load() + ssdn_plan_bind() rebuild them in one caller-owned arena; ssdn_train_step() / ssdn_net_forward() run them --
         a binder needs the library and this blob, not the Python package."""
+        if self.input_grad:
+            raise L.SsdnHipError("export_plan: input-gradient engines (the autograd route's) are not part of the plan blob")
         import json
         import struct
         tens: List[tuple] = []                       # (name, tensor)
@@ -720,12 +748,21 @@ class DenoiserEngine:
             self.g_fresh = self.loss_fwd = False
         self.main.fwd.run(s)
 
-    def backward(self, stream=None, exchange=None, defer_tail=False):
+    def _head_addend(self, on: bool) -> None:
+        """input_grad engines: whether the first network input gradient of the sum adds the head term the VJP left in `dx`"""
+        if not self.input_grad or self.pipeline != "ssdn":
+            return
+        first = self.sigma if self.sigma is not None else self.main
+        first.input_grad_args.add = _ptr(self.dx) if on else None
+
+    def backward(self, stream=None, exchange=None, defer_tail=False, with_head_dx=False):
         """Enqueue the backward pass.  exchange (ssdn.hip.dp.GradExchange, overlapped): the main net's list then carries one
         event record per gradient bucket; the last bucket (sigma estimator / learnable sigma) is marked after its own list.
         defer_tail (single-GPU training step only): the last bucket's slab reductions are left to the NEXT adam() call, which runs
-        them in front of the optimiser launch -- the flat gradient is incomplete until then."""
+        them in front of the optimiser launch -- the flat gradient is incomplete until then.
+        with_head_dx (vjp_backward(want_dx=True)): the input gradient adds the head term the VJP has just written into `dx`."""
         s = current_stream() if stream is None else stream
+        self._head_addend(with_head_dx)
         if defer_tail and exchange is None and self.ops_opt_tail is not None:
             if self.sigma is not None and (int(self.SIGMA_CONCURRENT) & 2):
                 ev = self._fork_sigma(s, self.sigma.bwd)
@@ -735,6 +772,7 @@ class DenoiserEngine:
                 self.main.bwd_head.run(s)
                 if self.sigma is not None:
                     self.sigma.bwd.run(s)
+            self._held_input_grad(s)
             self._tail_pending = True
             return
         self._tail_pending = False
@@ -756,15 +794,22 @@ class DenoiserEngine:
                 self.sigma.bwd.run(s)
             if len(exchange.ranges) > NB:
                 exchange.record_here(NB)
+            self._held_input_grad(s)
             return
         if self.sigma is not None and (int(self.SIGMA_CONCURRENT) & 2):
             ev = self._fork_sigma(s, self.sigma.bwd)
             self.main.bwd.run(s)
             self._join_sigma(s, ev)
-            return
-        self.main.bwd.run(s)
-        if self.sigma is not None:
-            self.sigma.bwd.run(s)
+        else:
+            self.main.bwd.run(s)
+            if self.sigma is not None:
+                self.sigma.bwd.run(s)
+        self._held_input_grad(s)
+
+    def _held_input_grad(self, s: int) -> None:
+        """mode var with input_grad: the main network's SSDN_OP_INPUT_GRAD, behind both backward lists (it adds the sigma network's)"""
+        if self.main.input_grad_ops is not None:
+            self.main.input_grad_ops.run(s)
 
     # ---- autograd: any upstream gradient of the pipeline outputs (SSDN_OP_HEAD_VJP / SSDN_OP_MSE_VJP) -------------------------------
     def _vjp_setup(self):
@@ -792,13 +837,17 @@ class DenoiserEngine:
             self._vjp = (a, OpList([("mse_vjp", a)]))
 
     def vjp_backward(self, w: Optional[torch.Tensor] = None, g_pme: Optional[torch.Tensor] = None, g_mu: Optional[torch.Tensor] = None,
-                     stream=None):
+                     stream=None, want_dx: bool = False):
         """Backward pass for ANY upstream gradient of the last training forward: w = dL/dLOSS [B] (or [B,1]), g_pme = dL/dIMG_DENOISED,
         g_mu = dL/dIMG_MU (ssdn), [B,C,H,W]; None = no gradient for that output.  Enqueues the VJP op (the loss gradient g32, the
         sigma partials and g_est), then the backward lists.  w == 1/B alone (mean(LOSS)) leaves the forward's loss gradient in place
-        (decided on the device): then the result is bit-identical to backward()."""
+        (decided on the device): then the result is bit-identical to backward().
+        want_dx (engines built with input_grad=True): the pass also leaves dL/d(noisy input) in `self.dx` (the head's direct term via
+        the VJP's g_noisy, then the networks' input gradients).  The parameter gradients are the same, bit for bit, either way."""
         if not self.train:
             raise L.SsdnHipError("vjp_backward needs a training engine")
+        if want_dx and not self.input_grad:
+            raise L.SsdnHipError("vjp_backward(want_dx=True) needs an engine built with input_grad=True")
         if self._vjp is None:
             self._vjp_setup()
         a, ops = self._vjp
@@ -814,13 +863,14 @@ class DenoiserEngine:
             if g_mu is not None:
                 self.vjp_g_mu.copy_(g_mu, non_blocking=True)
                 a.g_mu = _ptr(self.vjp_g_mu)
+            a.g_noisy = _ptr(self.dx) if want_dx else None
         elif g_mu is not None:
             raise L.SsdnHipError("the %s pipeline has no IMG_MU" % self.pipeline)
         a.keep = int(self.g_fresh)
         s = current_stream() if stream is None else stream
         ops.run(s)
         self.g_fresh = False
-        self.backward(stream=s)
+        self.backward(stream=s, with_head_dx=want_dx and self.pipeline == "ssdn")
 
     def adam(self, lr: float, step: int, gscale: float = 1.0, stream=None):
         for a in self._adam_args:
