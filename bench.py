@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- training patches/sec of the ssdn hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1: one rank per GPU over RCCL.  Launched by `torch.distributed.run` (RANK / WORLD_SIZE / LOCAL_RANK in the environment) the
 script is a rank; launched plainly with --gpus N > 1 it re-executes itself under `torch.distributed.run --nnodes=1
@@ -16,18 +16,23 @@ DataLoader workers of the trainer deliver, 393 KB), is uploaded, and noise / rot
 device (`ssdn.datasets.DevicePatchStream`, the trainer's default data path on a GPU).
 
 Prints ONE JSON line (rank 0) with `value` = whole-job patches/s of that loop, plus
-  value_resident / value_with_fp32_h2d: the same step with the prepared batch already in HBM / arriving as fp32 noisy + clean
-                from pinned host memory (the reference's DataLoader format); side legs of >= 50 steps each, N = 1 only;
   roofline:     the dominant kernel (k_cdma<3,*>: the 96-output-channel 3x3 convolutions at 32x32 and 64x64 pixels, forward
                 and data-gradient role), timed with HIP events on the launch stream inside the timed region
-                (ssdn_profile_*), against the dense fp16 MFMA peak of /opt/skills/guides/MI355X_MICROARCH.md;
-  families:     the other MFMA kernel families the same way, after the timed region (k_conv by block size, k_gdma, k_wgrad);
+                (ssdn_profile_*), against the MI355X's dense fp16 MFMA peak (MFMA_FP16_DENSE_PEAK_TFLOPS);
   dump_outputs: with --dump-outputs DIR, what the timed path returned in its LAST timed step (the dictionary of
                 Denoiser.train_step, its input batch included) and the weights that step left, written as DIR/<name>.npy
                 (float32 / float64, at most 64 MB in all; rank 0).  Seeds are fixed: the same arguments give the same inputs, so
                 two builds can be compared output for output.
+A plain run stops there: set-up, warm-up, the timed steps, the dump, the line.  With --full it goes on, after the timed region
+(never in `value`), with the measurements that take steps or runs of their own:
+  value_resident / value_with_fp32_h2d: the same step with the prepared batch already in HBM / arriving as fp32 noisy + clean
+                from pinned host memory (the reference's DataLoader format); side legs of >= 50 steps each, N = 1 only;
+  value_trainer_hdf5: DenoiserTrainer.train() end to end over a synthetic HDF5 file (N = 1; --no-trainer-leg skips it);
+  families:     the other MFMA kernel families the same way as the roofline kernel (k_conv by block size, k_gdma, k_wgrad),
+                and roofline.second_kernel from them; roofline.algorithmic_bytes_per_launch on its exact basis (one extra step);
+  allreduce:    N > 1: how long the optimiser waits for the gradient exchange (allreduce_exposed_us), over 20 extra steps;
   cpu_baseline: the CPU oracle (oracle/restate.py, torch-CPU fp32, the operator family the reference runs on) timed on
-                this box's host cores on a bounded sample of the same workload (N=1, rank 0 only).
+                the host's cores on a bounded sample of the same workload (N=1, rank 0 only; --no-cpu-baseline skips it).
 """
 import argparse
 import ctypes as C
@@ -413,11 +418,12 @@ def run_rank(args):
         L.check(lib.ssdn_profile_read(prof_kind, C.byref(ms), C.byref(cnt), C.byref(fl), C.byref(by)))
         lib.ssdn_profile_enable(prof_kind, 0)
 
-    # ---- after the timed region (does not touch `value`) ----------------------------------------------------------------
+    # ---- after the timed region (does not touch `value`; --full only: a plain run prints its line next) -----------------------
+    full = args.full
     # (a) per-family table: every MFMA kernel family bracketed at stride 3 over a few extra steps
     families = {}
     FAM_STEPS, FAM_STRIDE = 30, 3        # (ten samples of a once-per-step launch: with four, one disturbed sample moved the average by 80 %)
-    if lib is not None:
+    if lib is not None and full:
         for name, kind in L.PROF.items():
             lib.ssdn_profile_enable(kind, 80 * FAM_STEPS // FAM_STRIDE + 64)
             lib.ssdn_profile_set_stride(kind, FAM_STRIDE)
@@ -437,7 +443,7 @@ def run_rank(args):
     # the eight launches of a step the samples fell on -- 109.9 MB in a 20-step run, 116.9 MB in a 100-step one): ONE extra step with every
     # launch of the family counted, i.e. the exact mean over the step's eight launches (inputs read once + outputs written once)
     alg_bytes_exact = None
-    if lib is not None:
+    if lib is not None and full:
         lib.ssdn_profile_enable(prof_kind, 64)
         lib.ssdn_profile_set_stride(prof_kind, 1)
         step(0)
@@ -450,7 +456,7 @@ def run_rank(args):
     # (a2) N > 1: how long the optimiser stream WAITS for the gradient exchange behind the last slab reduction (events on the compute
     # stream around launch + finish of ssdn.hip.dp.exchange_step: last k_wreduce_multi -> k_adam_pack), median of EXP_STEPS extra steps
     exposed = None
-    if exchange is not None:
+    if exchange is not None and full:
         EXP_STEPS = 20
         exchange.measure_exposed(True)
         samples = []
@@ -470,7 +476,7 @@ def run_rank(args):
     # (kernel-only rate), and the reference's DataLoader format (fp32 noisy + clean from pinned host memory, 2 x 1.6 MB per step)
     resident_value = fp32_value = None
     SIDE_STEPS = max(50, args.steps // 2)
-    if world == 1 and not stub:
+    if world == 1 and not stub and full:
         side = DevicePatchStream(None, nd, device, seed=2, rank=rank)         # (not attached: four distinct resident batches)
         res_batches = [side.prepare(u8[i], idx) for i in range(len(u8))]
 
@@ -497,7 +503,7 @@ def run_rank(args):
     # converter's layout -- forked DataLoader workers cropping at read (uint8), pinned upload, device noise, training step, the
     # per-step metrics on the device, console / scalar logging at PRINT_INTERVAL.  Timed from step TR_WARM to the last step.
     trainer_value = trainer_info = None
-    if world == 1 and not stub and not args.no_trainer_leg:
+    if world == 1 and not stub and full and not args.no_trainer_leg:
         try:
             trainer_value, trainer_info = trainer_leg(B, P, max(200, args.steps), workers=args.trainer_workers)
         except Exception as e:  # noqa: BLE001 -- a side leg must never cost the line its `value`
@@ -549,6 +555,7 @@ def run_rank(args):
         }
         if world > 1:
             res["config"]["backend"] = backend or "nccl (RCCL)"
+        if world > 1 and full:
             res["allreduce_exposed_us"] = exposed["allreduce_exposed_us"] if exposed else None
             res["allreduce"] = exposed
         if stub:
@@ -561,10 +568,13 @@ def run_rank(args):
                                "traffic_unit": "HBM-side bytes per launch, rocprofv3 FETCH_SIZE*2 + WRITE_SIZE from separate --pmc passes over this "
                                                "command; NOT measured in this run: %s" % traffic_src,
                                "algorithmic_bytes_per_launch": alg_bytes_exact if alg_bytes_exact else int(by.value / max(1, cnt.value)),
-                               "algorithmic_bytes_basis": "mean over ALL launches of the family in one step (every input read once + every output written once; one extra step after the timed region with every launch counted)",
+                               "algorithmic_bytes_basis": "mean over ALL launches of the family in one step (every input read once + every output written once; one extra step after the timed region with every launch counted)"
+                                                          if alg_bytes_exact else
+                                                          "mean over the sampled launches of the timed region (every input read once + every output written once; depends on which layers the samples fell on: the exact basis needs --full)",
                                "launches": int(cnt.value), "sampling": "every %dth launch of the timed region; the two HIP events of a sample ride on the sampled launch's own dispatch (hipExtLaunchKernelGGL start / stop event: the kernel's duration as a kernel trace reports it)" % PROF_STRIDE, "avg_launch_us": round(1e3 * ms.value / max(1, cnt.value), 3),
                                "kernel_time_share": round(PROF_STRIDE * ms.value / 1e3 / dt, 4)}
-            res["families"] = families
+            if full:
+                res["families"] = families
             # the time-dominant family next to the flop-dominant one: the weight gradients of the whole network,
             # ONE chip-wide launch per step (k_wgrad_mega), bracketed in the family leg after the timed region
             wg = families.get("wgrad")
@@ -585,7 +595,7 @@ def run_rank(args):
             res["trainer_hdf5"] = trainer_info
         if dumped is not None:
             res["dump_outputs"] = dumped
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if world == 1 and full and not args.no_cpu_baseline and not stub:
             res["cpu_baseline"] = cpu_baseline(P)
         print(json.dumps(res))
     if world > 1:
@@ -600,9 +610,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--batch", type=int, default=32, help="patches per GPU")
     ap.add_argument("--patch", type=int, default=64)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-trainer-leg", action="store_true", help="skip the value_trainer_hdf5 side leg (DenoiserTrainer.train() over an HDF5 file)")
-    ap.add_argument("--trainer-workers", type=int, default=8)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the side legs, the per-family kernel table, the exposed all-reduce (N > 1) "
+                         "and the CPU baseline (without it: set-up, warm-up, timed steps, dump and the result line only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-trainer-leg", action="store_true", help="with --full: skip the value_trainer_hdf5 side leg (DenoiserTrainer.train() over an HDF5 file)")
+    ap.add_argument("--trainer-workers", type=int, default=8, help="with --full: DataLoader workers of the trainer leg")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed (its returned arrays and the updated weights) as DIR/<name>.npy")
     args = ap.parse_args()

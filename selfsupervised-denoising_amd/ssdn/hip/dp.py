@@ -14,7 +14,7 @@ What overlaps depends on the plan (graph.WGRAD_MEGA).  Default plan "split": the
 complete when the side-lane weight-gradient launch and its reductions end, ~0.4 ms before the end of the backward pass: its
 all-reduce runs UNDER the rest of the backward pass.  Every other layer's gradient comes out of the chip-wide launch that closes
 the backward pass, so those three buckets complete together behind the final reduction run and are exchanged as ONE all-reduce
-(4.34 MB) that is EXPOSED in front of Adam (bench.py --gpus N reports it as `allreduce_exposed_us`); with a sigma estimator
+(4.34 MB) that is EXPOSED in front of Adam (bench.py --gpus N --full reports it as `allreduce_exposed_us`); with a sigma estimator
 (config 3) that network's backward pass follows and covers it.  Plan "buckets" (one launch per bucket, +0.12 ms per step on one
 GPU) overlaps every bucket but the last.  With world_size 1 nothing is communicated.
 

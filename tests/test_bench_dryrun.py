@@ -25,7 +25,7 @@ def _run(extra_env, *argv):
 
 
 def test_bench_gpus2_self_spawns_and_prints_one_line():
-    p, lines = _run({"SSDN_BENCH_STUB": "1"}, "--gpus", "2", "--steps", "3", "--warmup", "1")
+    p, lines = _run({"SSDN_BENCH_STUB": "1"}, "--gpus", "2", "--steps", "3", "--warmup", "1", "--full")
     assert p.returncode == 0, p.stderr[-3000:]
     assert len(lines) == 1, p.stdout
     r = json.loads(lines[0])
@@ -37,6 +37,26 @@ def test_bench_gpus2_self_spawns_and_prints_one_line():
     # N > 1: the line says how long the optimiser waited for the gradient exchange behind the backward pass
     assert r["allreduce_exposed_us"] is not None and r["allreduce_exposed_us"] >= 0 and r["allreduce"]["steps"] == 20
     assert sum(r["allreduce"]["collectives_per_step_bytes"]) == 4 * 1269129
+
+
+def test_bench_plain_run_leaves_the_extra_legs_to_full():
+    """A plain run prints the headline line without the measurements that take steps of their own; --full adds them (N > 1: the
+    exposed all-reduce over 20 extra steps) and leaves the headline fields as they are."""
+    p, lines = _run({"SSDN_BENCH_STUB": "1"}, "--gpus", "2", "--steps", "3", "--warmup", "1")
+    assert p.returncode == 0, p.stderr[-3000:]
+    assert len(lines) == 1, p.stdout
+    r = json.loads(lines[0])
+    assert r["n_gpus"] == 2 and r["steps"] == 3 and r["warmup"] == 1 and r["stub"] is True
+    assert r["value"] > 0 and r["unit"] == "patches/s" and r["higher_is_better"] is True and r["dtype"] == "f16"
+    assert abs(r["value"] - 3 * 64 / (r["ms_per_step"] * 3 / 1e3)) < 1e-2 * r["value"]
+    for k in ("allreduce_exposed_us", "allreduce", "families", "value_resident", "value_trainer_hdf5", "cpu_baseline"):
+        assert k not in r, k
+    p, lines = _run({"SSDN_BENCH_STUB": "1"}, "--gpus", "2", "--steps", "3", "--warmup", "1", "--full")
+    assert p.returncode == 0, p.stderr[-3000:]
+    f = json.loads(lines[-1])
+    assert f["allreduce"]["steps"] == 20
+    assert {k: f[k] for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup")} == \
+        {k: r[k] for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup")}
 
 
 def test_bench_dp_plan_is_echoed():

@@ -6,9 +6,9 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/final
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp
-# 1. un-profiled bench lines (the numbers the other files are compared with): long run, and the driver's default flags
-timeout 600 python $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline > $OUT/bench_line.json 2> $OUT/bench_line.err
-timeout 600 python $R/bench.py --steps 20 --warmup 5 > $OUT/bench_line_default_flags.json 2> $OUT/bench_line_default_flags.err
+# 1. un-profiled bench lines (the numbers the other files are compared with), with every leg (--full): long run, and the driver's step counts
+timeout 600 python $R/bench.py --steps 100 --warmup 10 --full --no-cpu-baseline > $OUT/bench_line.json 2> $OUT/bench_line.err
+timeout 600 python $R/bench.py --steps 20 --warmup 5 --full > $OUT/bench_line_default_flags.json 2> $OUT/bench_line_default_flags.err
 # 2. kernel trace + stats of the bench command
 timeout 300 rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-trainer-leg > $OUT/kt.log 2>&1
 cp $(find $OUT/kt -name "*kernel_stats.csv" | head -1) $OUT/bench_kernel_stats.csv

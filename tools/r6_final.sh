@@ -23,5 +23,5 @@ for r in 1 2 3; do
     SSDN_HIP_LIB=$LIBV timeout 600 python bench.py --steps 100 --warmup 20 --no-cpu-baseline --no-trainer-leg 2>&1 | grep -v amdgpu.ids | python -c "import sys, json; d = json.loads(sys.stdin.read().strip().splitlines()[-1]); print('patches/s', d['value'], 'ms_per_step', d['ms_per_step'], 'k_cdma<3,*> TF/s', d['roofline']['achieved'], 'frac', d['roofline']['frac'])" >> $OUT/ab_round5_library.txt 2>&1
   done
 done
-SSDN_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 50 --warmup 10 --no-cpu-baseline --no-trainer-leg > $OUT/bench_2rank_gloo_one_gpu.json 2> $OUT/bench_2rank_gloo_one_gpu.err
+SSDN_BENCH_BACKEND=gloo timeout 600 python bench.py --gpus 2 --steps 50 --warmup 10 --full --no-cpu-baseline --no-trainer-leg > $OUT/bench_2rank_gloo_one_gpu.json 2> $OUT/bench_2rank_gloo_one_gpu.err
 ls -la $OUT
