@@ -35,7 +35,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SSDN_ABI_VERSION 17
+#define SSDN_ABI_VERSION 18
 #define SSDN_MAX_TAPS 9
 
 /* NHWC fp16 view: element (n,y,x,c) lives at p[((n*H + y)*W + x)*cs + co + c]. */
@@ -329,7 +329,10 @@ typedef struct ssdn_grad_pack_args {
  *   g_net_out [B,Cout,H,W] = d mean(LOSS) / d net_out, partial[b][chunk][2] = {sum loss, sum dloss/dest_raw} per workgroup,
  *   gmax = atomicMax of |g| float bits.
  * HEAD_FINAL sums the partials in fixed order: loss[b] = mean over pixels; g_est (const: [1], var: [B]);
- *   for var also fills g_sigma_out [B,1,H,W] with g_est[b]/(H*W) (gradient of the spatial mean) and folds it into gmax2. */
+ *   for var also fills g_sigma_out [B,1,H,W] with g_est[b]/(H*W) (gradient of the spatial mean) and folds it into gmax2.
+ * diag (ABI 18): 0 = the full covariance above; 1 = DIAGONAL_COVARIANCE: Cout = 2*C, net_out = [mu_c, a_c], Sigma_x = diag(a_c^2),
+ *   per-channel closed forms, g_net_out [B,2*C,H,W]; with C = 1 both are the same model (bit for bit).
+ *   C must be 1 or 3. */
 typedef struct ssdn_head_args {
     const float* net_out; /* [B,Cout,H,W] */
     const float* noisy;   /* [B,C,H,W] */
@@ -346,6 +349,7 @@ typedef struct ssdn_head_args {
     float* partial;
     int32_t nchunks;
     uint32_t* gmax;
+    int32_t diag;         /* ABI 18: 1 = diagonal covariance (see above), 0 = full */
 } ssdn_head_args;
 
 typedef struct ssdn_head_final_args {
@@ -393,7 +397,8 @@ typedef struct ssdn_mse_args {
  * with no g_pme / g_mu and w[b] == 1.f/B exactly keeps them untouched (the check runs on the device), so mean(LOSS) under autograd
  * is bit-identical to the planned backward pass at every batch size.  Every reduction is in a fixed order: bit-reproducible.
  * g_noisy (ABI 17; NULL = not computed, every other output unchanged bit for bit): HEAD_VJP also writes the head's DIRECT term of
- * dL/dnoisy [B,C,H,W] -- net_out and sigma held fixed; a sample that keeps g_net_out (keep) still writes it. */
+ * dL/dnoisy [B,C,H,W] -- net_out and sigma held fixed; a sample that keeps g_net_out (keep) still writes it.
+ * diag (ABI 18): the forward's diag (SSDN_OP_HEAD_SSDN): 1 = the diagonal-covariance head, net_out / g_net_out [B,2*C,H,W]. */
 typedef struct ssdn_head_vjp_args {
     const float* net_out; /* [B,Cout,H,W] */
     const float* noisy;   /* [B,C,H,W] */
@@ -413,6 +418,7 @@ typedef struct ssdn_head_vjp_args {
     float* g_sigma_out;   /* var: [B,1,H,W] */
     uint32_t* gmax2;      /* var */
     float* g_noisy;       /* [B,C,H,W] or NULL (ABI 17) */
+    int32_t diag;         /* ABI 18: = the forward's */
 } ssdn_head_vjp_args;
 
 typedef struct ssdn_mse_vjp_args {

@@ -47,12 +47,42 @@ static __device__ __forceinline__ float sigmoid_m4(float raw) {
     return x > 20.f ? 1.f : 1.f / (1.f + expf(-x));
 }
 
+// ---- DIAGONAL_COVARIANCE: C = 3, net_out = [mu_0..2, a_0..2], Sigma_x = diag(a_c^2).  Every quantity is per
+// channel: sy_c = a_c^2 + sigma_c^2, no adjugate.  (C = 1 is the same model with or without the flag: its runs use the DIAG = false code.)
+// sigma_c of one channel (k_head's rules) and its derivatives by mu_c and by the softplus'd estimate
+static __device__ __forceinline__ void diag_sigma(int style, int mode, float npar, float est, float mu, float& sig, float& dsig_dmu,
+                                                  float& dsig_dest) {
+    if (style == 0) {
+        sig = mode == 0 ? fmaxf(npar, 1e-3f) : est;
+        dsig_dmu = 0.f;
+        dsig_dest = 1.f;
+    } else {
+        float m = fmaxf(mu, 1e-3f);
+        float f = mode == 0 ? 1.f / npar : est;
+        sig = sqrtf(m * f);
+        dsig_dmu = mu > 1e-3f ? 0.5f * f / sig : 0.f;
+        dsig_dest = 0.5f * m / sig;
+    }
+}
+// posterior mean of one channel, the reference's three eps-regularised inverses written for diagonal matrices:
+//   pme = (mu ix + y in) / (ix + in + eps) = mu u + y v,   ix = 1/(sx + eps), in = 1/(sn + eps), u = ix rD, v = in rD, rD = 1/(ix + in + eps)
+static __device__ __forceinline__ float diag_pme_weights(float sx, float sn, float& ix, float& in, float& u, float& v) {
+    const float e = 1e-6f;
+    ix = 1.f / (sx + e);
+    in = 1.f / (sn + e);
+    const float rD = 1.f / (ix + in + e);
+    u = ix * rD;
+    v = in * rD;
+    return rD;
+}
+
+template <bool DIAG>
 __global__ void k_head(ssdn_head_args a) {
     __shared__ float sh[4];
     const int b = blockIdx.y;
     const long long HW = (long long)a.H * a.W;
     const int C = a.C;
-    const int Cout = C + C * (C + 1) / 2;
+    const int Cout = DIAG ? 2 * C : C + C * (C + 1) / 2;
     const float inv_total = 1.f / ((float)a.B * (float)HW);  // mean over pixels, then mean over the batch
     float est = 0.f, dest_draw = 0.f;
     if (a.mode != 0) {
@@ -68,7 +98,57 @@ __global__ void k_head(ssdn_head_args a) {
     const float* no = a.net_out + (long long)b * Cout * HW;
     const float* ny = a.noisy + (long long)b * C * HW;
     for (long long p = p0 + threadIdx.x; p < p1; p += HB) {
-        if (C == 1) {
+        if constexpr (DIAG) {
+            // l = 1/2 log(max(0, sy_0 sy_1 sy_2)) + 1/2 sum_c d_c^2 / sy_c  (- 0.1 mean_c sigma_c)
+            float mu[3], av[3], sig[3], dsig_dmu[3], dsig_dest[3], sx[3], sn[3], rs[3], q[3];
+            float prod = 1.f, quad = 0.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                mu[c] = no[c * HW + p];
+                av[c] = no[(3 + c) * HW + p];
+                diag_sigma(a.style, a.mode, npar, est, mu[c], sig[c], dsig_dmu[c], dsig_dest[c]);
+                sx[c] = av[c] * av[c];
+                sn[c] = sig[c] * sig[c];
+                const float sy = sx[c] + sn[c], d = ny[c * HW + p] - mu[c];
+                rs[c] = 1.f / sy;
+                q[c] = d * rs[c];                                  // d_c / sy_c
+                prod *= sy;
+                quad += d * q[c];
+            }
+            float l = 0.5f * logf(fmaxf(prod, 0.f)) + 0.5f * quad;
+            if (a.mode != 0) l -= 0.1f * (sig[0] + sig[1] + sig[2]) * (1.f / 3.f);
+            loss_acc += l;
+            long long o3 = (long long)b * 3 * HW + p;
+            if (a.mu) { a.mu[o3] = mu[0]; a.mu[o3 + HW] = mu[1]; a.mu[o3 + 2 * HW] = mu[2]; }
+            if (a.pme) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    float ix, in, u, v;
+                    diag_pme_weights(sx[c], sn[c], ix, in, u, v);
+                    a.pme[o3 + c * HW] = mu[c] * u + ny[c * HW + p] * v;
+                }
+            }
+            if (a.model_std) a.model_std[(long long)b * HW + p] = cbrtf(fabsf(av[0] * av[1] * av[2]));   // (prod sx_c)^(1/6)
+            if (a.noise_std && a.style == 1) a.noise_std[(long long)b * HW + p] = cbrtf(sig[0] * sig[1] * sig[2]);
+            if (a.want_grad) {
+                // dl/dsy_c = 1/2 [prod > 0] / sy_c - 1/2 q_c^2; sx_c and sn_c enter through sy_c alone
+                const float hd = prod > 0.f ? 0.5f : 0.f;
+                const float reg = a.mode != 0 ? 0.1f / 3.f : 0.f;
+                float gs = 0.f;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float gsy = hd * rs[c] - 0.5f * q[c] * q[c];
+                    const float ds = 2.f * sig[c] * gsy - reg;
+                    const float gmu = (-q[c] + ds * dsig_dmu[c]) * inv_total;
+                    const float ga = 2.f * av[c] * gsy * inv_total;
+                    a.g_net_out[((long long)b * 6 + c) * HW + p] = gmu;
+                    a.g_net_out[((long long)b * 6 + 3 + c) * HW + p] = ga;
+                    gabs = fmaxf(gabs, fmaxf(fabsf(gmu), fabsf(ga)));
+                    gs += ds * dsig_dest[c];
+                }
+                gest_acc += gs;
+            }
+        } else if (C == 1) {
             float mu = no[p], av = no[HW + p], y = ny[p];
             float sig, dsig_dmu = 0.f, dsig_dest = 0.f;
             if (a.style == 0) {
@@ -203,9 +283,12 @@ __global__ void k_head(ssdn_head_args a) {
         a.noise_std[b] = a.mode == 0 ? fmaxf(npar, 1e-3f) : est;
 }
 int launch_head(const ssdn_head_args* a, hipStream_t s) {
+    if (a->diag && a->C != 1 && a->C != 3) return ssdn_set_error("head: diag needs C = 1 or 3");
     if (a->C != 1 && a->C != 3) return ssdn_set_error("head: C must be 1 or 3 (denoiser.py:199)");
+    if (a->diag != 0 && a->diag != 1) return ssdn_set_error("head: diag must be 0 or 1");
     if (a->nchunks < 1) return ssdn_set_error("head: nchunks < 1");
-    hipLaunchKernelGGL(k_head, dim3(a->nchunks, a->B), dim3(HB), 0, s, *a);
+    if (a->diag && a->C == 3) hipLaunchKernelGGL(k_head<true>, dim3(a->nchunks, a->B), dim3(HB), 0, s, *a);
+    else hipLaunchKernelGGL(k_head<false>, dim3(a->nchunks, a->B), dim3(HB), 0, s, *a);
     return 0;
 }
 
@@ -512,6 +595,24 @@ static __device__ __forceinline__ void head_dy_pixel(const ssdn_head_vjp_args& a
     }
     gy[p] = v0; gy[HW + p] = v1; gy[2 * HW + p] = v2;
 }
+// DIAG: per channel, LOSS sc d_c/sy_c, posterior mean g_c v_c (v_c = in_c / (ix_c + in_c + eps), diag_pme_weights)
+static __device__ __forceinline__ void head_dy_pixel_diag(const ssdn_head_vjp_args& a, const float* no, const float* ny, const float* gp,
+                                                          float* gy, long long p, long long HW, float sc, float npar, float est) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float mu = no[c * HW + p], av = no[(3 + c) * HW + p];
+        float sig, dsig_dmu, dsig_dest;
+        diag_sigma(a.style, a.mode, npar, est, mu, sig, dsig_dmu, dsig_dest);
+        float sx = av * av, sn = sig * sig;
+        float v = sc != 0.f ? (ny[c * HW + p] - mu) / (sx + sn) * sc : 0.f;
+        if (gp) {
+            float ix, in, u, w;
+            diag_pme_weights(sx, sn, ix, in, u, w);
+            v += gp[c * HW + p] * w;
+        }
+        gy[c * HW + p] = v;
+    }
+}
 // Same grid and pixel chunking as k_head, so partial[b][chunk][1] lands where the forward put it.  A sample whose request is exactly
 // the forward's d mean(LOSS) (keep, no g_pme / g_mu, w[b] == 1.f/B) leaves its gradient and partials alone, bit for bit: it returns at
 // once, or, when g_noisy is requested, after writing only that.
@@ -519,13 +620,14 @@ static __device__ __forceinline__ void head_dy_pixel(const ssdn_head_vjp_args& a
 // its inputs instead of sharing the first pass's values: extra uses of those would let the compiler contract the g_net_out arithmetic
 // differently, and the other outputs must not depend on GY, bit for bit.  The GY = true instance declares its real workgroup size (HB):
 // under the default bound of 1024 threads (128 VGPRs) it spilled to scratch.
-template <bool GY>
+// DIAG: the diagonal-covariance head of k_head<true> (C = 3, Cout = 6), per-channel closed forms.
+template <bool GY, bool DIAG>
 __global__ __attribute__((amdgpu_flat_work_group_size(1, GY ? HB : 1024))) void k_head_vjp(ssdn_head_vjp_args a) {
     __shared__ float sh[4];
     const int b = blockIdx.y;
     const long long HW = (long long)a.H * a.W;
     const int C = a.C;
-    const int Cout = C + C * (C + 1) / 2;
+    const int Cout = DIAG ? 2 * C : C + C * (C + 1) / 2;
     const float wb = a.w ? a.w[b] : 0.f;
     const bool skip = a.keep && !a.g_pme && !a.g_mu && a.w && wb == 1.f / (float)a.B;
     if (skip && !GY) return;                         // (block-uniform: before any barrier)
@@ -549,7 +651,57 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, GY ? HB : 1024))) void 
     float* go = a.g_net_out + (long long)b * Cout * HW;
     const long long p1v = GY && skip ? p0 : p1;        // (a kept sample: no first pass)
     for (long long p = p0 + threadIdx.x; p < p1v; p += HB) {
-        if (C == 1) {
+        if constexpr (DIAG) {
+            // per channel: dsx = dL/dsx_c, dn = dL/dsn_c, gmu = dL/dmu_c without the sigma chain
+            float mu[3], av[3], y[3], sig[3], dsig_dmu[3], dsig_dest[3], sx[3], sn[3], dsx[3], dn[3], gmu[3];
+            float prod = 1.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                mu[c] = no[c * HW + p];
+                av[c] = no[(3 + c) * HW + p];
+                y[c] = ny[c * HW + p];
+                diag_sigma(a.style, a.mode, npar, est, mu[c], sig[c], dsig_dmu[c], dsig_dest[c]);
+                sx[c] = av[c] * av[c];
+                sn[c] = sig[c] * sig[c];
+                prod *= sx[c] + sn[c];
+                dsx[c] = dn[c] = gmu[c] = 0.f;
+            }
+            float rg = 0.f;
+            if (sc != 0.f) {            // LOSS: dl/dsy_c = 1/2 [prod > 0] / sy_c - 1/2 q_c^2, dl/dmu_c = -q_c, q_c = d_c / sy_c
+                const float hd = prod > 0.f ? 0.5f : 0.f;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float rs = 1.f / (sx[c] + sn[c]), q = (y[c] - mu[c]) * rs;
+                    dsx[c] = dn[c] = (hd * rs - 0.5f * q * q) * sc;
+                    gmu[c] = -q * sc;
+                }
+                rg = reg * (1.f / 3.f) * sc;
+            }
+            if (gp) {                   // posterior mean mu u + y v: d/dmu = u, d/dsx = (pme - mu) ix u, d/dsn = (pme - y) in v
+                const float e = 1e-6f;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    float ix, in, u, v;
+                    const float re = e * diag_pme_weights(sx[c], sn[c], ix, in, u, v);        // eps rD
+                    const float g = gp[c * HW + p], d = y[c] - mu[c];
+                    gmu[c] += g * u;
+                    dsx[c] += g * (d * v - mu[c] * re) * ix * u;            // pme - mu = d v - mu eps rD (no cancellation)
+                    dn[c] -= g * (d * u + y[c] * re) * in * v;              // pme - y = -(d u + y eps rD)
+                }
+            }
+            float gs = 0.f;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float ds = 2.f * sig[c] * dn[c] - rg;
+                const float gm_c = gmu[c] + ds * dsig_dmu[c] + (gm ? gm[c * HW + p] : 0.f);
+                const float ga = 2.f * av[c] * dsx[c];
+                go[c * HW + p] = gm_c;
+                go[(3 + c) * HW + p] = ga;
+                gabs = fmaxf(gabs, fmaxf(fabsf(gm_c), fabsf(ga)));
+                gs += ds * dsig_dest[c];
+            }
+            gest_acc += gs;
+        } else if (C == 1) {
             float mu = no[p], av = no[HW + p], y = ny[p];
             float sig, dsig_dmu = 0.f, dsig_dest = 0.f;
             if (a.style == 0) {
@@ -680,7 +832,10 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, GY ? HB : 1024))) void 
     }
     if constexpr (GY) {
         float* gy = a.g_noisy + (long long)b * C * HW;
-        for (long long p = p0 + threadIdx.x; p < p1; p += HB) head_dy_pixel(a, no, ny, gp, gy, p, HW, sc, npar, est);
+        for (long long p = p0 + threadIdx.x; p < p1; p += HB) {
+            if constexpr (DIAG) head_dy_pixel_diag(a, no, ny, gp, gy, p, HW, sc, npar, est);
+            else head_dy_pixel(a, no, ny, gp, gy, p, HW, sc, npar, est);
+        }
         if (skip) return;               // (block-uniform: the sample's g_net_out and partials stay the forward's)
     }
     float gs = block_sum(gest_acc, sh);
@@ -703,14 +858,20 @@ __global__ void k_head_vjp_final(ssdn_head_vjp_args a) {
     }
 }
 int launch_head_vjp(const ssdn_head_vjp_args* a, hipStream_t s) {
+    if (a->diag && a->C != 1 && a->C != 3) return ssdn_set_error("head_vjp: diag needs C = 1 or 3");
     if (a->C != 1 && a->C != 3) return ssdn_set_error("head_vjp: C must be 1 or 3");
+    if (a->diag != 0 && a->diag != 1) return ssdn_set_error("head_vjp: diag must be 0 or 1");
     if (a->B < 1 || a->H < 1 || a->W < 1 || a->nchunks < 1) return ssdn_set_error("head_vjp: bad shape");
     if (a->mode < 0 || a->mode > 2 || a->style < 0 || a->style > 1) return ssdn_set_error("head_vjp: bad style / mode");
     if (!a->net_out || !a->noisy || !a->g_net_out || !a->partial) return ssdn_set_error("head_vjp: net_out, noisy, g_net_out and partial must be given");
     if (a->mode == 0 && !a->noise_param) return ssdn_set_error("head_vjp: mode known needs noise_param");
     if (a->mode != 0 && !a->est_raw) return ssdn_set_error("head_vjp: modes const / var need est_raw");
-    if (a->g_noisy) hipLaunchKernelGGL(k_head_vjp<true>, dim3(a->nchunks, a->B), dim3(HB), 0, s, *a);
-    else hipLaunchKernelGGL(k_head_vjp<false>, dim3(a->nchunks, a->B), dim3(HB), 0, s, *a);
+    const dim3 grid(a->nchunks, a->B);
+    if (a->diag && a->C == 3) {
+        if (a->g_noisy) hipLaunchKernelGGL((k_head_vjp<true, true>), grid, dim3(HB), 0, s, *a);
+        else hipLaunchKernelGGL((k_head_vjp<false, true>), grid, dim3(HB), 0, s, *a);
+    } else if (a->g_noisy) hipLaunchKernelGGL((k_head_vjp<true, false>), grid, dim3(HB), 0, s, *a);
+    else hipLaunchKernelGGL((k_head_vjp<false, false>), grid, dim3(HB), 0, s, *a);
     if (a->mode != 0 && a->g_est) {
         hipLaunchKernelGGL(k_head_vjp_final, dim3((a->B + 63) / 64), dim3(64), 0, s, *a);
         if (a->mode == 2 && a->g_sigma_out) {

@@ -94,10 +94,13 @@ class Denoiser(nn.Module):
         C = cfg[ConfigValue.IMAGE_CHANNELS]
         self._pipeline = cfg[ConfigValue.PIPELINE]
         ssdn_pipe = self._pipeline == Pipeline.SSDN
-        if ssdn_pipe and cfg.get(ConfigValue.DIAGONAL_COVARIANCE):
-            # the reference's diagonal branch raises (`c00.shape()`, denoiser.py:240) and is unreachable from its CLI
-            raise NotImplementedError("DIAGONAL_COVARIANCE is broken in the reference (denoiser.py:240) and not supported")
-        cout = C + (C * (C + 1)) // 2 if ssdn_pipe else C               # means + triangular A (denoiser.py:55-64)
+        # DIAGONAL_COVARIANCE: means + the diagonal of A (denoiser.py:57-58; the loss head of DESIGN.md section 3.10 -- the reference's own
+        # diagonal branch raises at `c00.shape()`, denoiser.py:240).  The MSE pipelines ignore it, as the reference does.
+        self._diag = bool(ssdn_pipe and cfg.get(ConfigValue.DIAGONAL_COVARIANCE))
+        if self._diag:
+            cout = 2 * C
+        else:
+            cout = C + (C * (C + 1)) // 2 if ssdn_pipe else C           # means + triangular A (denoiser.py:55-64)
         self._var = ssdn_pipe and cfg[ConfigValue.NOISE_VALUE] == NoiseValue.UNKNOWN_VARIABLE
         self._const = ssdn_pipe and cfg[ConfigValue.NOISE_VALUE] == NoiseValue.UNKNOWN_CONSTANT
         blind = cfg[ConfigValue.BLINDSPOT]
@@ -186,7 +189,8 @@ class Denoiser(nn.Module):
             eng = DenoiserEngine(self._pipeline.value, cfg[ConfigValue.IMAGE_CHANNELS], cfg[ConfigValue.BLINDSPOT],
                                  cfg.get(ConfigValue.NOISE_STYLE) or "gauss", cfg[ConfigValue.NOISE_VALUE].value if self._pipeline == Pipeline.SSDN else "known",
                                  B, H, W, self.device, self.flat, self.flat_grad, self.adam_m, self.adam_v,
-                                 self._n_main, self._n_sig, self._const, train=train, ncoords=ncoords, input_grad=input_grad)
+                                 self._n_main, self._n_sig, self._const, train=train, ncoords=ncoords, input_grad=input_grad,
+                                 diag=self._diag)
             self._engines[key] = [eng, None]
             while len(self._engines) > _MAX_ENGINES:         # LRU: a plan owns ~1 GB of buffers at BASELINE sizes
                 old = next(k for k in self._engines if k != key)

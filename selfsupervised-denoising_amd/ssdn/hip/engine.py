@@ -466,10 +466,13 @@ class DenoiserEngine:
 
     def __init__(self, pipeline: str, channels: int, blindspot: bool, style: str, mode: str, B: int, H: int, W: int,
                  device, params: torch.Tensor, grads: torch.Tensor, adam_m: torch.Tensor, adam_v: torch.Tensor,
-                 n_main: int, n_sigma: int, has_est: bool, train: bool = True, ncoords: int = 64, input_grad: bool = False):
+                 n_main: int, n_sigma: int, has_est: bool, train: bool = True, ncoords: int = 64, input_grad: bool = False,
+                 diag: bool = False):
         if input_grad and not train:
             raise ValueError("input_grad needs a training engine (train=True)")
         self.pipeline, self.C, self.blindspot, self.mode = pipeline, channels, blindspot, mode
+        # DIAGONAL_COVARIANCE (ssdn): the network's 2*C outputs are the means and the diagonal of A
+        self.diag = bool(diag) and pipeline == "ssdn"
         self.input_grad = bool(input_grad)
         self.style = "poisson" if style.startswith("poisson") else "gauss"
         self.B, self.H, self.W, self.device, self.train = B, H, W, device, train
@@ -478,7 +481,7 @@ class DenoiserEngine:
         cus = lib.ssdn_device_cus()
         if cus <= 0:
             raise L.SsdnHipError("no HIP device: " + lib.ssdn_last_error().decode())
-        cout = channels + channels * (channels + 1) // 2 if pipeline == "ssdn" else channels
+        cout = (2 * channels if self.diag else channels + channels * (channels + 1) // 2) if pipeline == "ssdn" else channels
         f32 = dict(dtype=torch.float32, device=device)
         self.inp = torch.zeros((B, channels, H, W), **f32)
         var = pipeline == "ssdn" and mode == "var"
@@ -556,7 +559,7 @@ class DenoiserEngine:
             recs.append(("head_ssdn", L.HeadArgs(_ptr(out32), _ptr(self.inp), _ptr(self.noise_param), est_ptr, B, Cn, H, W,
                                                   STYLE[self.style], MODE[self.mode], int(want_grad), _ptr(self.mu), _ptr(self.pme),
                                                   _ptr(self.model_std), _ptr(self.noise_std), g32, _ptr(self.partial),
-                                                  self.nchunks, self._gmax(self.main))))
+                                                  self.nchunks, self._gmax(self.main), int(self.diag))))
             g_est = None
             if want_grad and self.mode == "const":
                 g_est = _ptr(self.grads, 4 * self.est_off)
@@ -679,7 +682,7 @@ class DenoiserEngine:
                   [self.main.bwd, self.sigma.bwd if self.sigma is not None else None] if train else [],
                   [self.ops_opt] if train else []]
         layers = lambda net, base: [dict(name=l.name, w_off=base + l.w_off, b_off=base + l.b_off, M=l.M, cin=l.cin, k=l.k) for l in net.plan.layers]   # noqa: E731
-        desc = dict(pipeline=self.pipeline, channels=self.C, blindspot=bool(self.blindspot), style=self.style, mode=self.mode, B=self.B, H=self.H,
+        desc = dict(pipeline=self.pipeline, channels=self.C, blindspot=bool(self.blindspot), style=self.style, mode=self.mode, diag=self.diag, B=self.B, H=self.H,
                     W=self.W, train=bool(train), nparams=int(self.params.numel()), est_off=self.est_off,
                     layers=layers(self.main, 0) + (layers(self.sigma, self.sigma.plan.param_base) if self.sigma is not None else []))
         desc.update(meta or {})
@@ -825,6 +828,7 @@ class DenoiserEngine:
             a.net_out, a.noisy, a.noise_param = _ptr(self.main.tensor("out32")), _ptr(self.inp), _ptr(self.noise_param)
             a.B, a.C, a.H, a.W, a.style, a.mode = B, Cn, H, W, STYLE[self.style], MODE[self.mode]
             a.nchunks, a.g_net_out, a.partial, a.gmax = self.nchunks, g32, _ptr(self.partial), self._gmax(self.main)
+            a.diag = int(self.diag)
             if self.mode == "const":
                 a.est_raw, a.g_est = _ptr(self.params, 4 * self.est_off), _ptr(self.grads, 4 * self.est_off)
             elif self.mode == "var":

@@ -83,7 +83,7 @@ class GradPackArgs(C.Structure):
 class HeadArgs(C.Structure):
     _fields_ = [("net_out", vp), ("noisy", vp), ("noise_param", vp), ("est_raw", vp), ("B", i32), ("C", i32), ("H", i32),
                 ("W", i32), ("style", i32), ("mode", i32), ("want_grad", i32), ("mu", vp), ("pme", vp), ("model_std", vp),
-                ("noise_std", vp), ("g_net_out", vp), ("partial", vp), ("nchunks", i32), ("gmax", vp)]
+                ("noise_std", vp), ("g_net_out", vp), ("partial", vp), ("nchunks", i32), ("gmax", vp), ("diag", i32)]
 
 
 class HeadFinalArgs(C.Structure):
@@ -133,7 +133,7 @@ class HeadVjpArgs(C.Structure):
     _fields_ = [("net_out", vp), ("noisy", vp), ("noise_param", vp), ("est_raw", vp), ("B", i32), ("C", i32), ("H", i32), ("W", i32),
                 ("style", i32), ("mode", i32), ("w", vp), ("g_pme", vp), ("g_mu", vp), ("keep", i32), ("nchunks", i32),
                 ("g_net_out", vp), ("partial", vp), ("gmax", vp), ("g_est", vp), ("g_sigma_out", vp), ("gmax2", vp),
-                ("g_noisy", vp)]
+                ("g_noisy", vp), ("diag", i32)]
 
 
 class MseVjpArgs(C.Structure):
@@ -148,7 +148,7 @@ ARG_TYPES = dict(pack_input=PackInputArgs, conv=ConvArgs, pool_fwd=PoolArgs, poo
                  input_grad=InputGradArgs, head_vjp=HeadVjpArgs, mse_vjp=MseVjpArgs)
 
 # every symbol include/ssdn_hip.h declares
-ABI_VERSION = 17      # SSDN_ABI_VERSION of include/ssdn_hip.h this binding mirrors
+ABI_VERSION = 18      # SSDN_ABI_VERSION of include/ssdn_hip.h this binding mirrors
 
 SYMBOLS = ["ssdn_run_ops", "ssdn_stream_order", "ssdn_conv_lds_bytes", "ssdn_wgrad_lds_bytes", "ssdn_abi_version", "ssdn_last_error",
            "ssdn_device_cus", "ssdn_probe_mfma", "ssdn_probe_tr16", "ssdn_struct_size", "ssdn_profile_enable",
