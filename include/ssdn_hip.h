@@ -35,7 +35,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define SSDN_ABI_VERSION 18
+#define SSDN_ABI_VERSION 19
 #define SSDN_MAX_TAPS 9
 
 /* NHWC fp16 view: element (n,y,x,c) lives at p[((n*H + y)*W + x)*cs + co + c]. */
@@ -70,7 +70,8 @@ enum ssdn_op_type {
     SSDN_OP_NOISE = 21,        /* training patch stream: uint8 clean patches -> noisy / clean / reference fp32 (+ Noise2Void) */
     SSDN_OP_INPUT_GRAD = 22,   /* gradient w.r.t. the network input (NoiseNetwork under autograd with x.requires_grad) */
     SSDN_OP_HEAD_VJP = 23,     /* vector-Jacobian product of the SSDN head: any upstream gradient of LOSS / posterior mean / mu */
-    SSDN_OP_MSE_VJP = 24       /* the same for the (masked) MSE pipelines: LOSS / network output */
+    SSDN_OP_MSE_VJP = 24,      /* the same for the (masked) MSE pipelines: LOSS / network output */
+    SSDN_OP_ACCUM = 25         /* dst[i] = fl(dst[i] + src[i]): folds a per-pass staging value into a running gradient sum */
 };
 
 /* One record of the op list.  `args` points at the matching ssdn_*_args struct (host memory).
@@ -276,7 +277,12 @@ typedef struct ssdn_wgrad_args {
  * gb[m] = inv_scale * sum_s bslab[s][m];  k(cin) = cin (cin < c0) else c0 + (cin - c0) i.e. padding removed:
  * real input channels are [0,c0) and [c0, c0+c1_real).  inv_scale is read from device memory (loss-scale word).
  * Slabs are summed in a fixed order (groups of 32 in index order, then the groups in order): bit-reproducible.
- * NOTE: the slab buffer is used as scratch (partial sums are written back into it). */
+ * NOTE: the slab buffer is used as scratch (partial sums are written back into it).
+ * accumulate = 1 (gradient accumulation over micro-batches): the epilogue ADDS instead of storing,
+ *   gw[o] = fl(gw[o] + fl(inv_scale * sum)),  gb[m] = fl(gb[m] + fl(inv_scale * sum)):
+ * the product is rounded first, then one fp32 add (no FMA), so the running sum is fl(old + g) with g bit for bit what
+ * accumulate = 0 stores.  Elements that accumulate = 0 does not write (padding, gb == NULL) stay untouched either way.
+ * The flag is a property of a RUN: the caller sets it on the argument structs, the planner's records do not carry it. */
 typedef struct ssdn_wreduce_args {
     const float* slab;
     const float* bslab;
@@ -288,6 +294,7 @@ typedef struct ssdn_wreduce_args {
     float* gw;
     float* gb; /* may be NULL (bias gradient is produced by one block column only) */
     const float* inv_scale; /* device scalar, may be NULL (=1) */
+    int32_t accumulate;     /* 0: store (overwrite gw / gb), 1: add to what gw / gb hold */
 } ssdn_wreduce_args;
 
 /* ---- SSDN_OP_WPACK --------------------------------------------------------------------------
@@ -477,6 +484,16 @@ typedef struct ssdn_zero_args {
     void* p;
     int64_t bytes;
 } ssdn_zero_args;
+
+/* ---- SSDN_OP_ACCUM ---------------------------------------------------------------------------
+ * dst[i] = fl(dst[i] + src[i]), i < n: one fp32 add per element.  An accumulating backward pass of a model with a learnable noise
+ * scalar (mode const) points g_est of SSDN_OP_HEAD_FINAL / SSDN_OP_HEAD_VJP at a one-float staging buffer and folds it into the flat
+ * gradient with this op, once per pass (those ops STORE g_est: writing the flat gradient directly would destroy the running sum). */
+typedef struct ssdn_accum_args {
+    float* dst;
+    const float* src;
+    int64_t n;
+} ssdn_accum_args;
 
 /* ---- SSDN_OP_EVENT_RECORD -------------------------------------------------------------------
  * Records the caller-owned hipEvent_t `event` on the stream of the op's lane, i.e. after every earlier op of that lane (and,

@@ -108,6 +108,7 @@ int ssdn_struct_size(int op_type) {
         case SSDN_OP_INPUT_GRAD: return (int)sizeof(ssdn_input_grad_args);
         case SSDN_OP_HEAD_VJP: return (int)sizeof(ssdn_head_vjp_args);
         case SSDN_OP_MSE_VJP: return (int)sizeof(ssdn_mse_vjp_args);
+        case SSDN_OP_ACCUM: return (int)sizeof(ssdn_accum_args);
         default: return -1;
     }
 }
@@ -376,6 +377,7 @@ int ssdn_run_ops(const ssdn_op* ops, int n, void* stream) {
             case SSDN_OP_INPUT_GRAD: arm(i + 1); rc = launch_input_grad((const ssdn_input_grad_args*)p, s); break;
             case SSDN_OP_HEAD_VJP: rc = launch_head_vjp((const ssdn_head_vjp_args*)p, s); break;
             case SSDN_OP_MSE_VJP: rc = launch_mse_vjp((const ssdn_mse_vjp_args*)p, s); break;
+            case SSDN_OP_ACCUM: rc = launch_accum((const ssdn_accum_args*)p, s); break;
             case SSDN_OP_ZERO: {
                 const ssdn_zero_args* z = (const ssdn_zero_args*)p;
                 if (z->bytes & 15) return ssdn_set_error("op %d: zero size must be a multiple of 16", i);

@@ -151,6 +151,7 @@ int launch_adam(const ssdn_adam_args* a, hipStream_t s);
 int adam_pack_fusable(const ssdn_adam_args* a, const ssdn_wpack_args* const* items, int n);
 int launch_adam_pack(const ssdn_adam_args* a, const ssdn_wpack_args* const* items, int n, hipStream_t s);
 int launch_metrics(const ssdn_metrics_args* a, hipStream_t s);
+int launch_accum(const ssdn_accum_args* a, hipStream_t s);
 int launch_noise(const ssdn_noise_args* a, hipStream_t s);
 int launch_input_grad(const ssdn_input_grad_args* a, hipStream_t s);   // input_grad.hip
 int conv_lds_bytes(const ssdn_conv_args* a);

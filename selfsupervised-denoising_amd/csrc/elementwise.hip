@@ -469,7 +469,10 @@ static __device__ __forceinline__ void wreduce_final(const ssdn_wreduce_args& a,
                 if (kj < klim && ci < a.cin) {
                     long long o = a.tapblock ? ((long long)(a.m_off + m) * a.cin_full + a.c_off + ci)
                                              : ((long long)(a.m_off + m) * a.cin_full + a.c_off + kj) * a.ntaps + t;
-                    a.gw[o] = r[j] * inv;
+                    // accumulate: product rounded first, then ONE fp32 add (never contracted into an FMA), so that the sum over
+                    // passes is fl(gw + g) with g exactly what the overwriting pass stores, for any inv_scale
+                    const float g = __fmul_rn(r[j], inv);
+                    a.gw[o] = a.accumulate ? __fadd_rn(a.gw[o], g) : g;
                 }
             }
         }
@@ -487,7 +490,8 @@ static __device__ __forceinline__ void wreduce_final(const ssdn_wreduce_args& a,
             for (int u = 0; u < 16; ++u) acc += v[u];
         }
         for (; s < a.nslabs; ++s) acc += a.bslab[(long long)s * a.Mpad + m];
-        a.gb[a.m_off + m] = acc * inv;
+        const float g = __fmul_rn(acc, inv);
+        a.gb[a.m_off + m] = a.accumulate ? __fadd_rn(a.gb[a.m_off + m], g) : g;
     }
 }
 __global__ void k_wreduce(ssdn_wreduce_args a, int step) {
@@ -580,6 +584,20 @@ int launch_wreduce(const ssdn_wreduce_args* a, hipStream_t s) {
     if (a->Kpad & 3) return ssdn_set_error("wreduce: Kpad must be a multiple of 4");
     long long n = stride / 4 + a->M;
     SSDN_LAUNCH(k_wreduce, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, s, *a, step);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// ACCUM: dst[i] = fl(dst[i] + src[i]) -- folds a per-pass staging value (the learnable-sigma gradient of an accumulating pass)
+// into the running sum of the flat gradient
+// ------------------------------------------------------------------------------------------------
+__global__ void k_accum(ssdn_accum_args a) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < a.n) a.dst[i] = __fadd_rn(a.dst[i], a.src[i]);
+}
+int launch_accum(const ssdn_accum_args* a, hipStream_t s) {
+    if (!a->dst || !a->src || a->n < 0) return ssdn_set_error("accum: dst and src must be given, n >= 0");
+    if (a->n > 0) hipLaunchKernelGGL(k_accum, dim3(ew_grid(a->n)), dim3(EW_BLOCK), 0, s, *a);
     return 0;
 }
 

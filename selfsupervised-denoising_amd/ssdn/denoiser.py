@@ -16,9 +16,22 @@ accumulates it into `.grad`.  Such a run uses a training plan with input gradien
 forward that `Denoiser.backward()` / `optimizer_step()` act on, and its outputs equal those of the same eval-mode run under no_grad.  Its backward takes ANY upstream gradient of them -- per-sample
 weights or other reductions of LOSS, a loss on the posterior mean or on mu, or several at once -- copies those that arrived into the
 engine and runs the vector-Jacobian product of the loss head on the GPU (SSDN_OP_HEAD_VJP / SSDN_OP_MSE_VJP), then the planned
-backward pass.  `torch.mean(LOSS).backward()` gives exactly the gradient of `Denoiser.backward()`.  As before, the parameters' `.grad`
-are views of the flat gradient buffer: every backward OVERWRITES them (no accumulation), so all terms of a loss must go through ONE
-`backward()` call -- eval-mode input-gradient graphs too.  A graph whose engine has since run another training forward (`run_pipeline`
+backward pass.  `torch.mean(LOSS).backward()` gives exactly the gradient of `Denoiser.backward()`.  The parameters' `.grad` are views
+of the flat gradient buffer.
+
+Gradient accumulation.  With `accumulate_grads = False` (the default) every backward OVERWRITES the flat gradient, so all terms of a
+loss go through ONE `backward()` call -- eval-mode input-gradient graphs too.  With `accumulate_grads = True`, `Denoiser.backward()`
+and the autograd node ADD into it until `zero_grad()` / `optimizer_step()`: torch's `.grad` semantics, so several losses may go through
+several backward calls (as forward, backward, forward, backward: a pass decides whether it adds when its FORWARD is enqueued, and in
+mode const a backward that must add although its forward has already overwritten the scalar's gradient raises).  The first pass into a clean buffer overwrites (there is no zero-fill
+launch and stale values never leak in); after passes 1..K the buffer holds fl(..fl(fl(g_1 + g_2) + g_3).. + g_K) element by
+element, g_k being bit for bit what pass k alone writes (the slab reductions add in their epilogue, ssdn_wreduce_args.accumulate; the
+learnable noise scalar goes through a staging float and SSDN_OP_ACCUM).  A `torch.optim` optimiser's
+`zero_grad(set_to_none=True)` drops the `.grad` handles without telling the module: a pass that finds them gone treats the buffer as
+clean.  `accumulate_step` adds one micro-batch (forward + loss + backward, no exchange, no optimiser step, no re-pack) whatever
+`accumulate_grads` says; the `train_step` that follows adds its own, exchanges once and steps Adam once on the MEAN over the
+micro-batches (gscale = 1 / ((n + 1) * world)).  The input gradient is per forward and never accumulated here (torch's AccumulateGrad
+does that for the caller).  A graph whose engine has since run another training forward (`run_pipeline`
 or `train_step` of the same shape, or another input-gradient run of that shape) raises RuntimeError on backward.  The planned route `Denoiser.backward()` consumes its forward: afterwards that forward's IMG_DENOISED
 and IMG_MU are plain tensors again (detached in place), as they always were on that route.  NOISE_STD_DEV and MODEL_STD_DEV, no_grad outputs, eval-mode outputs of an input that does not require
 grad and everything `train_step` returns carry no graph (train_step never computes an input gradient).  No gradient flows into the
@@ -133,6 +146,10 @@ class Denoiser(nn.Module):
         self._exchange = None                        # ssdn.hip.dp.GradExchange of train_step (data parallel)
         self._anchor = torch.zeros((), requires_grad=True)
         self._img_graph = None                       # (engine, generation, weak refs to IMG_DENOISED / IMG_MU) of the last autograd forward
+        # gradient accumulation: backward() and the autograd node add into flat_grad (torch's .grad semantics) instead of overwriting it
+        self.accumulate_grads = False
+        self._grad_terms = 0                         # backward results currently summed in flat_grad (0 = clean: the next pass overwrites)
+        self._grads_exposed = False                  # the parameters' .grad handles show flat_grad (_expose_grads)
 
     def _add(self, model_id: str, model: nn.Module):
         self._models[model_id] = model
@@ -173,6 +190,47 @@ class Denoiser(nn.Module):
         for m in self._models.values():
             if hasattr(m, "mark_dirty"):
                 m.mark_dirty()
+
+    # ---- gradient accumulation -------------------------------------------------------------------------------------
+    def zero_grad(self, set_to_none: bool = True):
+        """Marks the flat gradient clean: the next backward overwrites it (nothing is zero-filled for that), then nn.Module.zero_grad."""
+        self._grad_terms = 0
+        self._grads_exposed = False
+        n_tot = self._n_main + self._n_sig + (1 if self._const else 0)
+        if n_tot < self.flat_grad.numel():       # (the <= 3 padding floats behind the last parameter have no writer in any pass)
+            self.flat_grad[n_tot:].zero_()
+        return super().zero_grad(set_to_none=set_to_none)
+
+    def _adds(self, force: bool = False) -> bool:
+        """whether a pass enqueued now adds to flat_grad: accumulation is wanted (accumulate_grads, or force: accumulate_step / the
+        train_step behind it) and the buffer holds a sum.  A torch.optim zero_grad(set_to_none=True) has dropped the exposed `.grad`
+        handles (all at once: one check is enough) while the buffer kept the old sum: that counts as clean."""
+        if not (force or self.accumulate_grads) or self._grad_terms == 0:
+            return False
+        if self._grads_exposed:
+            net = self._models[Denoiser.MODEL]
+            if net.get_submodule(net.layers[0].name).weight.grad is None:
+                self._grad_terms, self._grads_exposed = 0, False
+                return False
+        return True
+
+    def _sync_accumulate(self, eng, adds: bool) -> bool:
+        """A backward whose forward was enqueued under the other decision (another shape's backward, or a zero_grad, came in between).
+        The slab reductions take the flag at any time.  Mode const: a forward that staged g_est can still overwrite (-> True: the caller
+        goes through the VJP, which rewrites g_est where it now points); one that stored it into the running sum cannot be undone."""
+        if eng.accumulate == adds:
+            return False
+        if eng.stages_est and adds:
+            raise RuntimeError("Denoiser: with a learnable noise scalar the forward of an accumulating backward must be enqueued after the "
+                               "backward before it (forward, backward, forward, backward): this forward overwrote the scalar's gradient")
+        eng.set_accumulate(adds)
+        return eng.stages_est
+
+    def _count_backward(self, adds: bool) -> None:
+        if self.accumulate_grads:
+            self._grad_terms = self._grad_terms + 1 if adds else 1
+        else:
+            self._grad_terms = 0
 
     def _param_version(self):
         return (self._version, self.flat._version)
@@ -225,7 +283,7 @@ class Denoiser(nn.Module):
         slot = self._engines.get((B, H, W, True, ncoords))
         return slot[0].inp if slot is not None else None
 
-    def _run(self, data: List, clone: bool, bridge: bool = True) -> Dict:
+    def _run(self, data: List, clone: bool, bridge: bool = True, accumulate: bool = False) -> Dict:
         if self._pipeline not in (Pipeline.MSE, Pipeline.SSDN, Pipeline.MASK_MSE):
             raise NotImplementedError("Unsupported processing pipeline")
         inp = data[NoisyDataset.INPUT]
@@ -266,6 +324,8 @@ class Denoiser(nn.Module):
                     c0 = coords[0].to(torch.int64)
                     c0 = torch.stack([c0[:, 0] % H, c0[:, 1] % W], 1)              # python-style negative indices wrap
                     eng.coords.copy_(c0, non_blocking=True)   # element 0's mask for everyone (n2v_loss.py:12)
+        if eng.train:                      # (whether this pass adds is decided here: in mode const the forward's loss op stores g_est)
+            eng.set_accumulate(self._adds(force=accumulate))
         if have_loss:
             eng.forward()
         else:
@@ -310,10 +370,13 @@ class Denoiser(nn.Module):
         eng = self._last_train_engine
         if eng is None or not eng.train:
             raise RuntimeError("backward() needs a preceding training-mode run_pipeline()")
-        if eng.g_fresh or not eng.loss_fwd:
+        adds = self._adds()
+        via_vjp = self._sync_accumulate(eng, adds)
+        if not eng.loss_fwd or (eng.g_fresh and not via_vjp):
             eng.backward()
         else:       # an autograd backward of this forward has replaced the loss gradient: the VJP of mean(LOSS) restores it
             eng.vjp_backward(w=torch.full((eng.B,), 1.0 / eng.B, device=self.device))
+        self._count_backward(adds)
         self._expose_grads()
         # this route consumes the forward: its IMG_DENOISED / IMG_MU leave the graph, as they were before autograd reached them, so code
         # written for the planned backward (run_pipeline, backward(), then numpy on the images) keeps working
@@ -329,7 +392,10 @@ class Denoiser(nn.Module):
                          want_dx: bool = False):
         if eng is None or not eng.train:
             raise RuntimeError("this output was not produced by a training-mode run_pipeline()")
+        adds = self._adds()
+        self._sync_accumulate(eng, adds)
         eng.vjp_backward(w, g_pme, g_mu, want_dx=want_dx)
+        self._count_backward(adds)
         self._expose_grads()
 
     def _expose_grads(self):
@@ -341,6 +407,7 @@ class Denoiser(nn.Module):
         if self._const:
             o = self._n_main + self._n_sig
             self.l_params[Denoiser.ESTIMATED_SIGMA].grad = self.flat_grad[o:o + 1].view(1, 1, 1, 1)
+        self._grads_exposed = True
 
     def optimizer_step(self, lr: float, grad_scale: float = 1.0):
         """Fused Adam (betas 0.9/0.99, eps 1e-8; train.py:100-107) over the flat buffer + re-pack of the fp16 MFMA shadows.
@@ -350,6 +417,7 @@ class Denoiser(nn.Module):
             raise RuntimeError("optimizer_step() needs a preceding training-mode run_pipeline()")
         self.adam_steps += 1
         eng.adam(lr, self.adam_steps, grad_scale)
+        self._grad_terms = 0                 # the sum is spent: the next backward overwrites
         # the kernel wrote the flat buffer through a raw pointer: bump our own counter (torch's did not move); the shadows of
         # THIS engine are fresh, other cached shapes and the nets' own forward engines re-pack lazily
         self.mark_dirty()
@@ -422,15 +490,31 @@ class Denoiser(nn.Module):
     def train_step(self, data: List, lr: float, exchange=None, metrics: bool = False) -> Dict:
         """One whole optimisation step on this GPU: forward + loss + backward + Adam.  exchange: `gradient_exchange(world)`
         for data parallelism -- the per-bucket all-reduces are issued behind events recorded inside the backward list, so
-        they overlap the rest of the backward pass; Adam waits for them and folds in 1 / world."""
+        they overlap the rest of the backward pass; Adam waits for them and folds in 1 / world.
+        Behind n `accumulate_step` calls it adds its own micro-batch to their sum, exchanges that sum (the marks exist in this pass only)
+        and steps Adam once with gscale = 1 / ((n + 1) * world): the update of the mean loss over the n + 1 micro-batches."""
         from ssdn.hip import dp
-        out = self._run(data, clone=False, bridge=False)
+        out = self._run(data, clone=False, bridge=False, accumulate=True)
         eng = self._last_train_engine
+        n = self._grad_terms if eng.accumulate else 0
         if metrics:                         # (reads the forward pass's outputs: enqueued in front of the backward pass)
             self.accumulate_metrics(data, "train")
         from ssdn.hip import engine as _engine
         scale = dp.exchange_step(lambda ex: eng.backward(exchange=ex, defer_tail=ex is None and _engine.DEFER_TAIL), self.flat_grad, exchange)
-        self.optimizer_step(lr, scale)
+        self.optimizer_step(lr, scale if n == 0 else 1.0 / ((n + 1) * (exchange.world if exchange is not None else 1)))
+        return out
+
+    def accumulate_step(self, data: List, metrics: bool = False) -> Dict:
+        """One micro-batch of a larger optimisation step: forward + loss + backward, the gradient ADDED to what the micro-batches since the
+        last optimiser step left in `flat_grad` (the first one overwrites).  No gradient exchange, no optimiser step, no re-pack of the
+        weight shadows: the `train_step` that closes the group does those once.  Returns what `train_step` returns."""
+        out = self._run(data, clone=False, bridge=False, accumulate=True)
+        eng = self._last_train_engine
+        if metrics:
+            self.accumulate_metrics(data, "train")
+        n = self._grad_terms if eng.accumulate else 0
+        eng.backward(defer_tail=False)       # (deferred reductions would read slabs that the next micro-batch overwrites)
+        self._grad_terms = n + 1
         return out
 
     # ---- optimiser state in the reference's torch.optim.Adam layout (train.py:725,744: `.training` checkpoints) ----------

@@ -91,6 +91,17 @@ class DeviceNet:
         self.tail_recs = [(r[0], r[1]) for r in self._bwd_recs[len(self._bwd_recs) - ntail:]] if 0 < ntail < len(self._bwd_recs) else []
         self.bwd_head = OpList(self._bwd_recs[:len(self._bwd_recs) - len(self.tail_recs)], lanes=True) if self.tail_recs else None
         self.pack = OpList([self._mat(op) for op in plan.pack])
+        self.accumulate = False
+
+    def set_accumulate(self, on: bool) -> None:
+        """Whether the next backward pass of this network ADDS its weight and bias gradients to the flat gradient (gradient accumulation
+        over micro-batches, ssdn_wreduce_args.accumulate) instead of storing them.  A property of a run, not of the plan: set on the
+        materialised SSDN_OP_WREDUCE argument structs, in place.  Every variant of the backward list (`bwd`, `bwd_head` + `tail_recs`, the
+        optimiser list that carries the deferred tail, a list with event marks) points at these same structs, so none is rebuilt."""
+        self.accumulate = bool(on)
+        for r in self._bwd_recs:
+            if r[0] == "wreduce":
+                r[1].accumulate = int(self.accumulate)
 
     def bwd_with_events(self, buckets, new_event):
         """Backward op list with SSDN_OP_EVENT_RECORD marks for the gradient exchange (ssdn.hip.dp).  buckets: list of sets of layer
@@ -521,6 +532,14 @@ class DenoiserEngine:
         self.noise_std = torch.zeros((B, H, W) if self.style == "poisson" else (B,), **f32)
         self.zero_buf = torch.zeros((8,), dtype=torch.int32, device=device)   # unused gmax sink for eval
         self._adam_args = None
+        # gradient accumulation (set_accumulate): a pass that ADDS to the flat gradient.  The learnable noise scalar of mode const has no
+        # slab reduction: SSDN_OP_HEAD_FINAL (in the FORWARD list) and SSDN_OP_HEAD_VJP store its gradient, so in an accumulating pass
+        # they store into this staging float and the backward pass folds it into the running sum with one SSDN_OP_ACCUM launch.
+        self.accumulate = False
+        self.stages_est = bool(train and pipeline == "ssdn" and mode == "const" and self.est_off is not None)
+        self.g_est_stage = torch.zeros((1,), **f32) if self.stages_est else None
+        self._head_final_args = None
+        self._accum_ops = None
         # H11: loss / PSNR / std-dev sums of a step go into a device-resident accumulator (SSDN_OP_METRICS); `per` holds the last
         # batch's per-sample values (the evaluator's per-image PSNR)
         self.metrics_per = torch.zeros((B, 8), **f32)
@@ -560,14 +579,11 @@ class DenoiserEngine:
                                                   STYLE[self.style], MODE[self.mode], int(want_grad), _ptr(self.mu), _ptr(self.pme),
                                                   _ptr(self.model_std), _ptr(self.noise_std), g32, _ptr(self.partial),
                                                   self.nchunks, self._gmax(self.main), int(self.diag))))
-            g_est = None
-            if want_grad and self.mode == "const":
-                g_est = _ptr(self.grads, 4 * self.est_off)
-            elif want_grad and self.mode == "var":
-                g_est = _ptr(self.g_est_var)
+            g_est = self._g_est_ptr() if want_grad else None
             recs.append(("head_final", L.HeadFinalArgs(_ptr(self.partial), B, self.nchunks, H, W, MODE[self.mode], _ptr(self.loss), g_est,
                                                         _ptr(self.sigma.tensor("g32")) if (want_grad and self.sigma is not None) else None,
                                                         self._gmax(self.sigma) if self.sigma is not None else None)))
+            self._head_final_args = recs[-1][1]
         elif self.pipeline == "mse":
             recs.append(("mse", L.MseArgs(_ptr(out32), _ptr(self.ref), None, 0, B, Cn, H, W, _ptr(self.loss), g32, self._gmax(self.main))))
         elif self.pipeline == "mask_mse":
@@ -576,6 +592,36 @@ class DenoiserEngine:
         else:
             raise NotImplementedError("Unsupported processing pipeline")
         return recs
+
+    def _g_est_ptr(self):
+        """where the head ops store the gradient of the noise estimate: const: the flat gradient's last element, or the staging float in
+        an accumulating pass; var: the per-sample buffer (per pass either way); known: nowhere"""
+        if self.mode == "const":
+            return _ptr(self.g_est_stage) if self.accumulate and self.stages_est else _ptr(self.grads, 4 * self.est_off)
+        if self.mode == "var":
+            return _ptr(self.g_est_var)
+        return None
+
+    def set_accumulate(self, on: bool) -> None:
+        """The passes from the next FORWARD on add their parameter gradients to the flat gradient buffer (on) or overwrite it (off, the
+        default).  Decided before the forward is enqueued: in mode const the forward's loss op already stores the noise scalar's
+        gradient.  Idempotent; mutates argument structs in place, rebuilds no list."""
+        on = bool(on)
+        if on == self.accumulate:
+            return
+        if on and not self.train:
+            raise L.SsdnHipError("set_accumulate needs a training engine")
+        self.accumulate = on
+        self.main.set_accumulate(on)
+        if self.sigma is not None:
+            self.sigma.set_accumulate(on)
+        if self.stages_est:
+            if self._head_final_args is not None and self._head_final_args.g_est:
+                self._head_final_args.g_est = self._g_est_ptr()
+            if self._vjp is not None:
+                self._vjp[0].g_est = self._g_est_ptr()
+            if on and self._accum_ops is None:
+                self._accum_ops = OpList([("accum", L.AccumArgs(_ptr(self.grads, 4 * self.est_off), _ptr(self.g_est_stage), 1))])
 
     def _opt_ops(self):
         """Fused Adam over the flat buffer, each range directly followed by the re-packs of the layers inside it: the executor
@@ -624,6 +670,12 @@ class DenoiserEngine:
         a binder needs the library and this blob, not the Python package."""
         if self.input_grad:
             raise L.SsdnHipError("export_plan: input-gradient engines (the autograd route's) are not part of the plan blob")
+        if self.accumulate:          # a blob always holds overwriting passes (accumulate = 0, g_est in the flat gradient)
+            self.set_accumulate(False)
+            try:
+                return self.export_plan(meta)
+            finally:
+                self.set_accumulate(True)
         import json
         import struct
         tens: List[tuple] = []                       # (name, tensor)
@@ -766,6 +818,8 @@ class DenoiserEngine:
         with_head_dx (vjp_backward(want_dx=True)): the input gradient adds the head term the VJP has just written into `dx`."""
         s = current_stream() if stream is None else stream
         self._head_addend(with_head_dx)
+        if self.accumulate and self.stages_est:     # grads[est_off] += this pass's g_est (the forward's, or the VJP's that replaced it)
+            self._accum_ops.run(s)
         if defer_tail and exchange is None and self.ops_opt_tail is not None:
             if self.sigma is not None and (int(self.SIGMA_CONCURRENT) & 2):
                 ev = self._fork_sigma(s, self.sigma.bwd)
@@ -830,7 +884,7 @@ class DenoiserEngine:
             a.nchunks, a.g_net_out, a.partial, a.gmax = self.nchunks, g32, _ptr(self.partial), self._gmax(self.main)
             a.diag = int(self.diag)
             if self.mode == "const":
-                a.est_raw, a.g_est = _ptr(self.params, 4 * self.est_off), _ptr(self.grads, 4 * self.est_off)
+                a.est_raw, a.g_est = _ptr(self.params, 4 * self.est_off), self._g_est_ptr()
             elif self.mode == "var":
                 a.est_raw, a.g_est = _ptr(self.est_raw), _ptr(self.g_est_var)
                 a.g_sigma_out, a.gmax2 = _ptr(self.sigma.tensor("g32")), self._gmax(self.sigma)

@@ -17,7 +17,7 @@ MAX_TAPS = 9
 OP = dict(pack_input=1, conv=2, pool_fwd=3, pool_bwd=4, upsum_bwd=5, unrot_fwd=6, unrot_bwd=7, wgrad=8, wreduce=9,
           wpack=10, grad_pack=11, head_ssdn=12, head_final=13, spatial_mean=14, mse=15, mask_mse=16, adam=17,
           metrics=18, zero=19, event_record=20, noise=21, input_grad=22, head_vjp=23,
-          mse_vjp=24)
+          mse_vjp=24, accum=25)
 
 i32, f32, vp = C.c_int32, C.c_float, C.c_void_p
 
@@ -67,7 +67,7 @@ class WgradArgs(C.Structure):
 class WreduceArgs(C.Structure):
     _fields_ = [("slab", vp), ("bslab", vp), ("nslabs", i32), ("ntaps", i32), ("M", i32), ("Mpad", i32), ("Kpad", i32),
                 ("cin", i32), ("cin_full", i32), ("m_off", i32), ("c_off", i32), ("tapblock", i32), ("gw", vp), ("gb", vp),
-                ("inv_scale", vp)]
+                ("inv_scale", vp), ("accumulate", i32)]
 
 
 class WpackArgs(C.Structure):
@@ -141,14 +141,18 @@ class MseVjpArgs(C.Structure):
                 ("W", i32), ("keep", i32), ("w", vp), ("g_pme", vp), ("g", vp), ("gmax", vp)]
 
 
+class AccumArgs(C.Structure):
+    _fields_ = [("dst", vp), ("src", vp), ("n", C.c_int64)]
+
+
 ARG_TYPES = dict(pack_input=PackInputArgs, conv=ConvArgs, pool_fwd=PoolArgs, pool_bwd=PoolArgs, upsum_bwd=UpsumArgs,
                  unrot_fwd=UnrotArgs, unrot_bwd=UnrotArgs, wgrad=WgradArgs, wreduce=WreduceArgs, wpack=WpackArgs,
                  grad_pack=GradPackArgs, head_ssdn=HeadArgs, head_final=HeadFinalArgs, spatial_mean=SpatialMeanArgs,
                  mse=MseArgs, mask_mse=MseArgs, adam=AdamArgs, metrics=MetricsArgs, zero=ZeroArgs, event_record=EventArgs, noise=NoiseArgs,
-                 input_grad=InputGradArgs, head_vjp=HeadVjpArgs, mse_vjp=MseVjpArgs)
+                 input_grad=InputGradArgs, head_vjp=HeadVjpArgs, mse_vjp=MseVjpArgs, accum=AccumArgs)
 
 # every symbol include/ssdn_hip.h declares
-ABI_VERSION = 18      # SSDN_ABI_VERSION of include/ssdn_hip.h this binding mirrors
+ABI_VERSION = 19      # SSDN_ABI_VERSION of include/ssdn_hip.h this binding mirrors
 
 SYMBOLS = ["ssdn_run_ops", "ssdn_stream_order", "ssdn_conv_lds_bytes", "ssdn_wgrad_lds_bytes", "ssdn_abi_version", "ssdn_last_error",
            "ssdn_device_cus", "ssdn_probe_mfma", "ssdn_probe_tr16", "ssdn_struct_size", "ssdn_profile_enable",

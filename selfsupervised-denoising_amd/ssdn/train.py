@@ -11,7 +11,9 @@ noise / model std x 255) are averaged over a print interval.
 What is different underneath: a step is `Denoiser.train_step` (planned HIP op lists + fused Adam; no autograd graph, no
 torch.optim); data parallelism is one process per GPU (`torch.distributed` env of torchrun): every rank draws the SAME global
 sampling order and takes its rows of each global minibatch (ssdn.hip.dp.shard_rows), gradients are all-reduced overlapped with
-the backward pass, rank 0 owns the run directory.  The optimiser state is stored in torch.optim.Adam's state-dict layout, so
+the backward pass, rank 0 owns the run directory.  `accumulate` = K > 1 (`--accumulate K`): one turn of the loop is one optimiser step
+over up to K minibatches (`Denoiser.accumulate_step` for all but the last, `train_step` for the last: one gradient exchange, one Adam
+step on the mean); the learning rate is read once per turn and the interval checks see group boundaries only.  The optimiser state is stored in torch.optim.Adam's state-dict layout, so
 `.training` files interchange with the reference.
 
 Reference defects decided here: the `self.test_dataself.test_data()` typo that breaks any run with a
@@ -99,6 +101,9 @@ class DenoiserTrainer:
         self._exchange = None
         self._shard: Optional[_RankShard] = None
         self.device_data = None          # None: device-side patch preparation whenever a GPU is present (see train_data)
+        # minibatches per optimiser step (gradient accumulation).  Not a ConfigValue (that enum is a pickle contract with the reference):
+        # K > 1 travels as the extra top-level key "accumulate" of a `.training` file
+        self.accumulate = 1
 
     # ---- target -----------------------------------------------------------------------------------------------------------
     @property
@@ -168,6 +173,11 @@ class DenoiserTrainer:
             logger.info("Loaded Validation Dataset.")
         if self.world > 1 and self._exchange is None:
             self._exchange = denoiser.gradient_exchange(self.world)
+        K = int(self.accumulate)
+        if K < 1:
+            raise ValueError("accumulate must be >= 1")
+        if K > 1:
+            logger.info("Gradient accumulation: %d minibatches of %d per optimiser step" % (K, self.cfg[ConfigValue.TRAIN_MINIBATCH_SIZE]))
         logger.info(separator())
         logger.info("TRAINING STARTED")
         logger.info(separator())
@@ -202,24 +212,32 @@ class DenoiserTrainer:
                 self.snapshot()
             if iteration >= self.cfg[ConfigValue.TRAIN_ITERATIONS]:
                 break
-            data = next(data_itr)
-            image_count = data[NoisyDataset.INPUT].shape[0]
-            denoiser.train()
-            # H11: on a GPU the step's metric sums stay on the device (one kernel inside train_step, SSDN_OP_METRICS) and come to the
-            # host when the trainer prints; the reference's per-step tensor arithmetic (train.py:205-218) is the CPU path
-            on_device = getattr(denoiser, "device", torch.device("cpu")).type == "cuda" and torch.is_tensor(data[NoisyDataset.METADATA].get(MD.CLEAN))
-            outputs = denoiser.train_step(data, self.learning_rate, self._exchange, **({"metrics": True} if on_device else {}))
-            train_history["n"] += image_count
-            if not on_device:
-                with torch.no_grad():
-                    train_history["loss"] += outputs[PipelineOutput.LOSS]
-                    for key, name in self.img_outputs(prefix="psnr").items():
-                        train_history[name] += self.calculate_psnr(outputs, key, False)
-                    for key in (PipelineOutput.NOISE_STD_DEV, PipelineOutput.MODEL_STD_DEV):
-                        if key in outputs:
-                            train_history[key.value] += outputs[key] * 255
-            # images consumed by the whole job: rows x world for a sharded minibatch, the true count for the un-sharded tail
-            self.state[StateValue.ITERATION] += self._shard.counts.popleft() if self._shard is not None else image_count
+            # one turn = one optimiser step = up to K minibatches; the learning rate is read once, before the first (K minibatches of B see
+            # the schedule of minibatches of K x B); a group cut short by TRAIN_ITERATIONS steps with the minibatches it has
+            lr = self.learning_rate
+            group = min(K, -(-(self.cfg[ConfigValue.TRAIN_ITERATIONS] - iteration) // self.cfg[ConfigValue.TRAIN_MINIBATCH_SIZE]))
+            for k in range(group):
+                data = next(data_itr)
+                image_count = data[NoisyDataset.INPUT].shape[0]
+                denoiser.train()
+                # H11: on a GPU the step's metric sums stay on the device (one kernel inside train_step, SSDN_OP_METRICS) and come to the
+                # host when the trainer prints; the reference's per-step tensor arithmetic (train.py:205-218) is the CPU path
+                on_device = getattr(denoiser, "device", torch.device("cpu")).type == "cuda" and torch.is_tensor(data[NoisyDataset.METADATA].get(MD.CLEAN))
+                if k + 1 < group:          # (no exchange, no optimiser step: the group's last minibatch does both, once)
+                    outputs = denoiser.accumulate_step(data, **({"metrics": True} if on_device else {}))
+                else:
+                    outputs = denoiser.train_step(data, lr, self._exchange, **({"metrics": True} if on_device else {}))
+                train_history["n"] += image_count
+                if not on_device:
+                    with torch.no_grad():
+                        train_history["loss"] += outputs[PipelineOutput.LOSS]
+                        for key, name in self.img_outputs(prefix="psnr").items():
+                            train_history[name] += self.calculate_psnr(outputs, key, False)
+                        for key in (PipelineOutput.NOISE_STD_DEV, PipelineOutput.MODEL_STD_DEV):
+                            if key in outputs:
+                                train_history[key.value] += outputs[key] * 255
+                # images consumed by the whole job: rows x world for a sharded minibatch, the true count for the un-sharded tail
+                self.state[StateValue.ITERATION] += self._shard.counts.popleft() if self._shard is not None else image_count
         logger.info(separator())
         logger.info("TRAINING FINISHED")
         logger.info(separator())
@@ -438,6 +456,8 @@ class DenoiserTrainer:
         # continues the noise stream instead of restarting it at offset 0 under a re-drawn key
         if isinstance(self.trainloader, DevicePatchStream):
             sd["device_stream"] = self.trainloader.state_dict()
+        if int(self.accumulate) > 1:             # (a K = 1 file keeps the key set it always had)
+            sd["accumulate"] = int(self.accumulate)
         return sd
 
     def load_state_dict(self, state_dict: Union[Dict, str]):
@@ -449,6 +469,7 @@ class DenoiserTrainer:
         self._train_iter = SamplingOrder.from_state_dict(state_dict["train_order_iter"])
         self.denoiser.load_optimizer_state_dict(state_dict["optimizer"])
         self._stream_state = state_dict.get("device_stream")
+        self.accumulate = int(state_dict.get("accumulate", 1))
         torch.set_rng_state(state_dict["rng"])
         if self.world > 1 and self.rank > 0:
             # the file holds rank 0's generator state: the other ranks continue from a state derived from it, not from a copy
