@@ -330,16 +330,23 @@ typedef struct ssdn_grad_pack_args {
 /* ---- SSDN_OP_HEAD_SSDN / SSDN_OP_HEAD_FINAL -------------------------------------------------
  * replaces: Denoiser._ssdn_pipeline (denoiser.py:218-397) and its autograd backward:
  * per-pixel Gaussian posterior algebra in closed form (3x3 SPD inverse/det by adjugate), fp32.
- *   style: 0 gauss, 1 poisson.   mode: 0 known, 1 const (one learnable scalar), 2 var (sigma-net, one value / sample)
- *   noise_param[b]: sigma (gauss) or lambda (poisson) for mode known.   est_raw: [1] (const) or [B] (var), pre-softplus.
- * Outputs (any may be NULL): mu / pme [B,C,H,W], model_std [B,H,W], noise_std [B] (gauss) or [B,H,W] (poisson),
+ *   style: 0 gauss, 1 poisson, 2 impulse.   mode: 0 known, 1 const (one learnable scalar), 2 var (sigma-net, one value / sample)
+ *   noise_param[b]: sigma (gauss), lambda (poisson) or alpha (impulse) for mode known.   est_raw: [1] (const) or [B] (var), pre-softplus.
+ * Outputs (any may be NULL): mu / pme [B,C,H,W], model_std [B,H,W], noise_std [B] (gauss, impulse: alpha) or [B,H,W] (poisson),
  *   g_net_out [B,Cout,H,W] = d mean(LOSS) / d net_out, partial[b][chunk][2] = {sum loss, sum dloss/dest_raw} per workgroup,
  *   gmax = atomicMax of |g| float bits.
  * HEAD_FINAL sums the partials in fixed order: loss[b] = mean over pixels; g_est (const: [1], var: [B]);
  *   for var also fills g_sigma_out [B,1,H,W] with g_est[b]/(H*W) (gradient of the spatial mean) and folds it into gmax2.
  * diag (ABI 18): 0 = the full covariance above; 1 = DIAGONAL_COVARIANCE: Cout = 2*C, net_out = [mu_c, a_c], Sigma_x = diag(a_c^2),
  *   per-channel closed forms, g_net_out [B,2*C,H,W]; with C = 1 both are the same model (bit for bit).
- *   C must be 1 or 3. */
+ *   C must be 1 or 3.
+ * style 2, IMPULSE (a new VALUE of `style`, no layout change: the ABI version stays; csrc/head_impulse.hip): with
+ *   probability alpha a pixel was replaced, in all channels, by a colour uniform on [0,1)^C.  alpha: known: clamp(noise_param[b], 1e-3,
+ *   0.999); const / var: min(softplus(est_raw - 4) + 1e-3, 0.999), no gradient through an active clamp.  With e = mu_x - 1/2:
+ *     mu_y = alpha/2 + (1 - alpha) mu_x,  Sigma_y = (1 - alpha) Sigma_x + alpha/12 I + alpha (1 - alpha) e e^T   (the mixture's moments)
+ *     l = 1/2 log det Sigma_y + 1/2 (y - mu_y)^T Sigma_y^-1 (y - mu_y)   (C = 1: log sy + d^2 / sy);  l -= 0.1 alpha for mode != known
+ *     pme = mu_x + w (y - mu_x),  w = sigmoid(log(1 - alpha) - log alpha + log N(y; mu_x, Sigma_x + 1e-6 I))
+ *   mu = mu_x, model_std as style 0, noise_std[b] = alpha.  diag = 1 with style 2 is an error. */
 typedef struct ssdn_head_args {
     const float* net_out; /* [B,Cout,H,W] */
     const float* noisy;   /* [B,C,H,W] */
@@ -405,7 +412,9 @@ typedef struct ssdn_mse_args {
  * is bit-identical to the planned backward pass at every batch size.  Every reduction is in a fixed order: bit-reproducible.
  * g_noisy (ABI 17; NULL = not computed, every other output unchanged bit for bit): HEAD_VJP also writes the head's DIRECT term of
  * dL/dnoisy [B,C,H,W] -- net_out and sigma held fixed; a sample that keeps g_net_out (keep) still writes it.
- * diag (ABI 18): the forward's diag (SSDN_OP_HEAD_SSDN): 1 = the diagonal-covariance head, net_out / g_net_out [B,2*C,H,W]. */
+ * diag (ABI 18): the forward's diag (SSDN_OP_HEAD_SSDN): 1 = the diagonal-covariance head, net_out / g_net_out [B,2*C,H,W].
+ * style 2 (impulse, see SSDN_OP_HEAD_SSDN): the same contract -- w, g_pme, g_mu, keep, g_est / g_sigma_out = dL/dest_raw through alpha,
+ *   g_noisy (y enters y - mu_y, log N(y; ..) and w (y - mu_x)); diag = 1 with style 2 is an error. */
 typedef struct ssdn_head_vjp_args {
     const float* net_out; /* [B,Cout,H,W] */
     const float* noisy;   /* [B,C,H,W] */
@@ -514,6 +523,10 @@ typedef struct ssdn_event_args {
  *                                                      unbatched CHW sample, i.e. per channel: noise.py:34-39,55-56)
  *     gauss:    noisy = clean + param * N(0,1)                       (param = std dev as a fraction of 1)
  *     poisson:  noisy = (clean * param + Poisson(1)) / param         (RATE-1 noise on lambda x: the reference's quirk, noise.py:101-104)
+ *     impulse:  noisy = Bernoulli(param) per PIXEL ? U[0,1)^C : clean   (style 2: one decision for all channels of a pixel, the untouched
+ *               pixel stays exactly u8 / 255; param = alpha in [0, 1], ONE draw per sample for a range, written to all C entries of
+ *               param[b*C + c]; C <= 3; clip has nothing to do; the decision and the colours are a pure function of (seed, offset,
+ *               stream, pixel), so the Noise2Void copy and ref32 work as for the other styles)
  *     clip:     noisy = min(max(noisy, 0), 1)
  * `ref32` (optional) is a second, independent realisation with its own parameter draw (the Noise2Noise / Noise2Void reference).  With n2v_box > 0 the
  * first realisation is manipulated like n2v_ups.manipulate: one pixel (c0, c1) per n2v_box x n2v_box box (c0 stratified over W,
@@ -532,7 +545,7 @@ typedef struct ssdn_noise_args {
     float* param_ref;     /* out [B*C] or NULL: the (independently drawn) parameter of the second realisation */
     int64_t* coords;      /* out [B, (W/box)*(H/box), 2] or NULL (required when n2v_box > 0) */
     int32_t B, C, H, W;
-    int32_t style;        /* 0 gauss, 1 poisson */
+    int32_t style;        /* 0 gauss, 1 poisson, 2 impulse */
     int32_t clip;
     float p_lo, p_hi;
     int32_t n2v_box;      /* 0: no manipulation */

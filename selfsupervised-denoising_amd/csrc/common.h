@@ -141,10 +141,12 @@ int launch_wpack_multi(const ssdn_wpack_args* const* items, int n, hipStream_t s
 int launch_wreduce_multi(const ssdn_wreduce_args* const* items, int n, hipStream_t s);
 int launch_grad_pack(const ssdn_grad_pack_args* a, hipStream_t s);
 int launch_head(const ssdn_head_args* a, hipStream_t s);
+int launch_head_impulse(const ssdn_head_args* a, hipStream_t s);          // head_impulse.hip: style 2, called by launch_head
 int launch_head_final(const ssdn_head_final_args* a, hipStream_t s);
 int launch_spatial_mean(const ssdn_spatial_mean_args* a, hipStream_t s);
 int launch_mse(const ssdn_mse_args* a, int masked, hipStream_t s);
 int launch_head_vjp(const ssdn_head_vjp_args* a, hipStream_t s);   // head.hip: any upstream gradient of the pipeline outputs
+int launch_head_vjp_impulse(const ssdn_head_vjp_args* a, hipStream_t s);  // head_impulse.hip: style 2's kernel, called by launch_head_vjp
 int launch_mse_vjp(const ssdn_mse_vjp_args* a, hipStream_t s);
 int launch_adam(const ssdn_adam_args* a, hipStream_t s);
 #define ADAM_PACK_MAX 24

@@ -883,12 +883,74 @@ __global__ void k_noise(ssdn_noise_args a) {
         if (a.param && x == 0 && y == 0) a.param[bc] = param;
     }
 }
+// Noise2Void: is (x, y) of sample b the selected pixel of its box, and if so which neighbour (rx, ry) does it copy?  (writes the box's coords.)
+// The selection of k_noise, restated: k_noise keeps its own copy so that its code stays, instruction for instruction, what it was.
+static __device__ __forceinline__ bool n2v_select(const ssdn_noise_args& a, int b, int x, int y, int& rx, int& ry) {
+    const int H = a.H, W = a.W;
+    bool blind = false;
+    rx = x; ry = y;
+    if (a.n2v_box > 0) {
+        const int box = a.n2v_box, n1 = H / box, i = x / box, j = y / box, cell = i * n1 + j;
+        const unsigned ce = (unsigned)(b * (W / box) * n1 + cell);
+        const Ph4 r = philox4x32_10(ce, NS_COORD, (unsigned)a.offset, (unsigned)(a.offset >> 32), (unsigned)a.seed, (unsigned)(a.seed >> 32));
+        int c0 = i * box + (int)(u01(r.v[0]) * (float)box), c1 = j * box + (int)(u01(r.v[1]) * (float)box);
+        c0 = c0 > i * box + box - 1 ? i * box + box - 1 : c0;
+        c1 = c1 > j * box + box - 1 ? j * box + box - 1 : c1;
+        if (c0 == x && c1 == y) {
+            blind = true;
+            rx = n2v_pick(c0, a.n2v_radius, W, u01(r.v[2]));
+            ry = n2v_pick(c1, a.n2v_radius, H, u01(r.v[3]));
+            a.coords[((long long)b * (W / box) * n1 + cell) * 2 + 0] = c0;
+            a.coords[((long long)b * (W / box) * n1 + cell) * 2 + 1] = c1;
+        }
+    }
+    return blind;
+}
+// IMPULSE (style 2): with probability alpha a pixel is replaced, in ALL channels, by a colour uniform on [0,1)^C; otherwise it stays exactly
+// u8 / 255 (clip has nothing to do).  One Philox draw per (pixel, realisation): word 0 decides, words 1..3 are the colour -- a pure function
+// of (seed, offset, stream, pixel), so the Noise2Void copy re-derives its neighbour's value like k_noise.  A ranged alpha is ONE draw per
+// sample (the mask is per pixel), written to all C entries of param.  A kernel of its own, for the same reason.
+__global__ void k_noise_impulse(ssdn_noise_args a) {
+    const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int H = a.H, W = a.W, HW = H * W;
+    if (idx >= (unsigned)(a.B * HW)) return;
+    const int x = idx % W, y = (idx / W) % H, b = idx / HW;
+    const unsigned char* u8 = (const unsigned char*)a.clean_u8;
+    int rx, ry;
+    n2v_select(a, b, x, y, rx, ry);
+    const float alpha = noise_param(a, b * a.C, NS_PARAM);
+    const unsigned src = (unsigned)(b * HW + ry * W + rx);            // the pixel whose noisy value lands here (itself unless blind)
+    const Ph4 r = philox4x32_10(src, NS_INPUT, (unsigned)a.offset, (unsigned)(a.offset >> 32), (unsigned)a.seed, (unsigned)(a.seed >> 32));
+    const bool hit = u01(r.v[0]) < alpha;
+    float alpha_ref = 0.f;
+    bool hit_ref = false;
+    Ph4 rr = r;
+    if (a.ref32) {
+        alpha_ref = noise_param(a, b * a.C, NS_PARAM_REF);
+        rr = philox4x32_10(idx, NS_REF, (unsigned)a.offset, (unsigned)(a.offset >> 32), (unsigned)a.seed, (unsigned)(a.seed >> 32));
+        hit_ref = u01(rr.v[0]) < alpha_ref;
+    }
+    for (int c = 0; c < a.C; ++c) {
+        const int bc = b * a.C + c;
+        const unsigned e = (unsigned)(bc * HW + y * W + x);
+        const float clean = (float)u8[e] / 255.f;
+        a.noisy32[e] = hit ? u01(r.v[1 + c]) : (float)u8[bc * HW + ry * W + rx] / 255.f;
+        if (a.clean32) a.clean32[e] = clean;
+        if (a.ref32) {
+            a.ref32[e] = hit_ref ? u01(rr.v[1 + c]) : clean;
+            if (a.param_ref && x == 0 && y == 0) a.param_ref[bc] = alpha_ref;
+        }
+        if (a.param && x == 0 && y == 0) a.param[bc] = alpha;
+    }
+}
 int launch_noise(const ssdn_noise_args* a, hipStream_t s) {
     if (!a->clean_u8 || !a->noisy32) return ssdn_set_error("noise: clean_u8 and noisy32 are required");
     if (a->B < 1 || a->C < 1 || a->H < 1 || a->W < 1) return ssdn_set_error("noise: empty shape");
     const long long n = (long long)a->B * a->C * a->H * a->W;
     if (n >= (1ll << 31)) return ssdn_set_error("noise: too many elements for 32-bit indexing");
-    if (a->style != 0 && a->style != 1) return ssdn_set_error("noise: style must be 0 (gauss) or 1 (poisson)");
+    if (a->style < 0 || a->style > 2) return ssdn_set_error("noise: style must be 0 (gauss), 1 (poisson) or 2 (impulse)");
+    if (a->style == 2 && a->C > 3) return ssdn_set_error("noise: impulse draws one colour of at most 3 channels per pixel");
+    if (a->style == 2 && !(a->p_lo >= 0.f && a->p_hi <= 1.f)) return ssdn_set_error("noise: impulse alpha must be inside [0, 1]");
     if (a->style == 1 && !(a->p_lo > 0.f)) return ssdn_set_error("noise: poisson lambda must be > 0");
     if (a->p_hi < a->p_lo) return ssdn_set_error("noise: p_hi < p_lo");
     if (a->n2v_box > 0) {
@@ -896,6 +958,7 @@ int launch_noise(const ssdn_noise_args* a, hipStream_t s) {
         if (a->H % a->n2v_box || a->W % a->n2v_box) return ssdn_set_error("noise: H and W must be multiples of n2v_box");
         if (a->n2v_radius < 1 || a->W < 2 || a->H < 2) return ssdn_set_error("noise: n2v_radius must be >= 1 and the patch larger than 1 pixel");
     }
-    hipLaunchKernelGGL(k_noise, dim3(ew_grid((long long)a->B * a->H * a->W)), dim3(EW_BLOCK), 0, s, *a);
+    if (a->style == 2) hipLaunchKernelGGL(k_noise_impulse, dim3(ew_grid((long long)a->B * a->H * a->W)), dim3(EW_BLOCK), 0, s, *a);
+    else hipLaunchKernelGGL(k_noise, dim3(ew_grid((long long)a->B * a->H * a->W)), dim3(EW_BLOCK), 0, s, *a);
     return 0;
 }

@@ -2,50 +2,7 @@
 // forward AND hand-derived backward, fp32 (gfx950).  Replaces Denoiser._ssdn_pipeline / _mse_pipeline /
 // _mask_mse_pipeline (/root/reference/ssdn/ssdn/denoiser.py:140-397, utils/n2v_loss.py:6-17) and their autograd graphs.
 // The math (closed-form 3x3 SPD algebra and its derivative) is documented in DESIGN.md section "posterior head".
-#include "common.h"
-
-#define HB 256
-
-static __device__ __forceinline__ float block_sum(float v, float* sh) {
-    // 256 threads = 4 waves of 64
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    int w = threadIdx.x >> 6, l = threadIdx.x & 63;
-    __syncthreads();
-    if (l == 0) sh[w] = v;
-    __syncthreads();
-    return sh[0] + sh[1] + sh[2] + sh[3];
-}
-static __device__ __forceinline__ void atomic_max_abs(uint32_t* gmax, float v) {
-    // |v| as uint is monotone in |v| for finite floats; one atomic per wave
-    float a = fabsf(v);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a = fmaxf(a, __shfl_down(a, o, 64));
-    if ((threadIdx.x & 63) == 0 && a > 0.f) atomicMax(gmax, __float_as_uint(a));
-}
-// ... one atomic per BLOCK (256 threads): the atomics of a launch all hit one address and serialise (~12 ns each); with one per wave a
-// launch of one pixel per thread spent more time in them than in its arithmetic
-static __device__ __forceinline__ void atomic_max_abs_block(uint32_t* gmax, float v, float* sh4) {
-    float a = fabsf(v);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a = fmaxf(a, __shfl_down(a, o, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = a;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const float m = fmaxf(fmaxf(sh4[0], sh4[1]), fmaxf(sh4[2], sh4[3]));
-        if (m > 0.f) atomicMax(gmax, __float_as_uint(m));
-    }
-}
-static __device__ __forceinline__ float softplus_m4(float raw) {
-    // torch.nn.Softplus(beta=1, threshold=20) applied to (raw - 4), + 1e-3   (denoiser.py:274-275)
-    float x = raw - 4.f;
-    return (x > 20.f ? x : log1pf(expf(x))) + 1e-3f;
-}
-static __device__ __forceinline__ float sigmoid_m4(float raw) {
-    float x = raw - 4.f;
-    return x > 20.f ? 1.f : 1.f / (1.f + expf(-x));
-}
+#include "head_common.h"
 
 // ---- DIAGONAL_COVARIANCE: C = 3, net_out = [mu_0..2, a_0..2], Sigma_x = diag(a_c^2).  Every quantity is per
 // channel: sy_c = a_c^2 + sigma_c^2, no adjugate.  (C = 1 is the same model with or without the flag: its runs use the DIAG = false code.)
@@ -287,6 +244,7 @@ int launch_head(const ssdn_head_args* a, hipStream_t s) {
     if (a->C != 1 && a->C != 3) return ssdn_set_error("head: C must be 1 or 3 (denoiser.py:199)");
     if (a->diag != 0 && a->diag != 1) return ssdn_set_error("head: diag must be 0 or 1");
     if (a->nchunks < 1) return ssdn_set_error("head: nchunks < 1");
+    if (a->style == 2) return launch_head_impulse(a, s);          // head_impulse.hip
     if (a->diag && a->C == 3) hipLaunchKernelGGL(k_head<true>, dim3(a->nchunks, a->B), dim3(HB), 0, s, *a);
     else hipLaunchKernelGGL(k_head<false>, dim3(a->nchunks, a->B), dim3(HB), 0, s, *a);
     return 0;
@@ -862,12 +820,14 @@ int launch_head_vjp(const ssdn_head_vjp_args* a, hipStream_t s) {
     if (a->C != 1 && a->C != 3) return ssdn_set_error("head_vjp: C must be 1 or 3");
     if (a->diag != 0 && a->diag != 1) return ssdn_set_error("head_vjp: diag must be 0 or 1");
     if (a->B < 1 || a->H < 1 || a->W < 1 || a->nchunks < 1) return ssdn_set_error("head_vjp: bad shape");
-    if (a->mode < 0 || a->mode > 2 || a->style < 0 || a->style > 1) return ssdn_set_error("head_vjp: bad style / mode");
+    if (a->mode < 0 || a->mode > 2 || a->style < 0 || a->style > 2) return ssdn_set_error("head_vjp: bad style / mode");
     if (!a->net_out || !a->noisy || !a->g_net_out || !a->partial) return ssdn_set_error("head_vjp: net_out, noisy, g_net_out and partial must be given");
     if (a->mode == 0 && !a->noise_param) return ssdn_set_error("head_vjp: mode known needs noise_param");
     if (a->mode != 0 && !a->est_raw) return ssdn_set_error("head_vjp: modes const / var need est_raw");
     const dim3 grid(a->nchunks, a->B);
-    if (a->diag && a->C == 3) {
+    if (a->style == 2) {                                             // head_impulse.hip; the reductions below serve it unchanged
+        if (int rc = launch_head_vjp_impulse(a, s)) return rc;
+    } else if (a->diag && a->C == 3) {
         if (a->g_noisy) hipLaunchKernelGGL((k_head_vjp<true, true>), grid, dim3(HB), 0, s, *a);
         else hipLaunchKernelGGL((k_head_vjp<false, true>), grid, dim3(HB), 0, s, *a);
     } else if (a->g_noisy) hipLaunchKernelGGL((k_head_vjp<true, false>), grid, dim3(HB), 0, s, *a);

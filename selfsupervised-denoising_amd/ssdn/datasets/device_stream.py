@@ -176,9 +176,12 @@ class DevicePatchStream:
             st = {"shape": torch.tensor([Cn, H, W]).repeat(B, 1), "null": torch.stack([NULL_IMAGE] * B).to(dev)}
             self._static = {key: st}
         kind, params, clip = noise.parse_style(ds.noise_style)
-        if kind not in ("gauss", "poisson"):
+        if kind not in ("gauss", "poisson", "impulse"):
             raise NotImplementedError("Noise type not supported")
-        vals = [(p / 255.0 if (kind == "gauss" and isinstance(p, int)) else float(p)) for p in params]
+        if kind == "impulse":                                   # integers are per cent; one alpha per sample in all C param entries
+            vals = [noise.impulse_alpha(p) for p in params]
+        else:
+            vals = [(p / 255.0 if (kind == "gauss" and isinstance(p, int)) else float(p)) for p in params]
         lo, hi = (vals[0], vals[0]) if len(vals) == 1 else (vals[0], vals[1])
         ranged = len(vals) > 1
         algo = ds.algorithm
@@ -206,7 +209,7 @@ class DevicePatchStream:
         a.param_ref = par_ref.data_ptr() if par_ref is not None else None
         a.coords = coords.data_ptr() if coords is not None else None
         a.B, a.C, a.H, a.W = B, Cn, H, W
-        a.style, a.clip, a.p_lo, a.p_hi = (0 if kind == "gauss" else 1), int(clip), lo, hi
+        a.style, a.clip, a.p_lo, a.p_hi = {"gauss": 0, "poisson": 1, "impulse": 2}[kind], int(clip), lo, hi
         a.n2v_box, a.n2v_radius = box, 5 // 2
         a.seed, a.offset = self.seed, self._calls
         self._calls += 1
@@ -257,6 +260,10 @@ class DevicePatchStream:
         def styled(x):
             # the reference draws a ranged noise parameter per leading index of a CHW sample, i.e. per CHANNEL (noise.py:
             # `_range_param`; reference utils/noise.py:34-39): fold the batch into that axis to get one draw per (sample, channel)
+            if noise.parse_style(ds.noise_style)[0] == "impulse":
+                # one decision per PIXEL and one alpha per sample; the coefficient takes the [B, C, 1, 1] layout of the other styles
+                y, c = noise.add_style(x, ds.noise_style, generator=g)
+                return y, (c.expand(B, C, 1, 1).contiguous() if torch.is_tensor(c) else c)
             y, c = noise.add_style(x.reshape(B * C, H, W), ds.noise_style, generator=g)
             return y.reshape(B, C, H, W), (c.reshape(B, C, 1, 1) if torch.is_tensor(c) else c)
         inp, inp_coeff = styled(clean)

@@ -110,6 +110,9 @@ class Denoiser(nn.Module):
         # DIAGONAL_COVARIANCE: means + the diagonal of A (denoiser.py:57-58; the loss head of DESIGN.md section 3.10 -- the reference's own
         # diagonal branch raises at `c00.shape()`, denoiser.py:240).  The MSE pipelines ignore it, as the reference does.
         self._diag = bool(ssdn_pipe and cfg.get(ConfigValue.DIAGONAL_COVARIANCE))
+        if self._diag and str(cfg.get(ConfigValue.NOISE_STYLE) or "").startswith("impulse"):
+            raise NotImplementedError("DIAGONAL_COVARIANCE is not implemented for the impulse noise model (the head refuses diag = 1 with "
+                                      "style = 2)")
         if self._diag:
             cout = 2 * C
         else:
@@ -351,9 +354,8 @@ class Denoiser(nn.Module):
         if self._pipeline == Pipeline.SSDN:
             out[PipelineOutput.IMG_MU] = pick(PipelineOutput.IMG_MU, eng.mu)
             out[PipelineOutput.IMG_DENOISED] = pick(PipelineOutput.IMG_DENOISED, eng.pme)
-            gauss = eng.style == "gauss"
             nstd = eng.noise_std
-            if gauss:
+            if eng.style != "poisson":                   # gauss: sigma, impulse: alpha -- one value per sample
                 nstd = nstd[:1].view(1, 1, 1) if self._const else nstd.view(B, 1, 1)
             out[PipelineOutput.NOISE_STD_DEV] = own(nstd)
             out[PipelineOutput.MODEL_STD_DEV] = own(eng.model_std)

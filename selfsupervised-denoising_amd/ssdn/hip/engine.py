@@ -467,8 +467,14 @@ HEAD_PX_PER_BLOCK = 1024
 # CU, one per CU: next to them nothing else runs, so they sit on the main lane (0), behind the data gradients whose results they read.
 MEGA_LANE = 0
 
-STYLE = {"gauss": 0, "poisson": 1}
+STYLE = {"gauss": 0, "poisson": 1, "impulse": 2}
 MODE = {"known": 0, "const": 1, "var": 2}
+
+
+def engine_style(style: str) -> str:
+    """the head's noise model of a style string: impulse (csrc/head_impulse.hip; NOISE_STD_DEV carries alpha, one value per sample like
+    gauss), poisson, and gauss for every other string, as ever"""
+    return "poisson" if style.startswith("poisson") else "impulse" if style.startswith("impulse") else "gauss"
 
 
 class DenoiserEngine:
@@ -485,7 +491,9 @@ class DenoiserEngine:
         # DIAGONAL_COVARIANCE (ssdn): the network's 2*C outputs are the means and the diagonal of A
         self.diag = bool(diag) and pipeline == "ssdn"
         self.input_grad = bool(input_grad)
-        self.style = "poisson" if style.startswith("poisson") else "gauss"
+        self.style = engine_style(style)
+        if self.style == "impulse" and self.diag:
+            raise NotImplementedError("DIAGONAL_COVARIANCE is not implemented for the impulse noise model")
         self.B, self.H, self.W, self.device, self.train = B, H, W, device, train
         self.params, self.grads, self.m, self.v = params, grads, adam_m, adam_v
         lib = L.load()
@@ -651,7 +659,7 @@ class DenoiserEngine:
             a.per = _ptr(self.metrics_per)
             if self.pipeline == "ssdn":
                 a.out, a.mu, a.model_std, a.noise_std = _ptr(self.pme), _ptr(self.mu), _ptr(self.model_std), _ptr(self.noise_std)
-                # (gauss: one value per sample -- one for the whole batch when sigma is a learnt constant; poisson: per pixel)
+                # (gauss, impulse: one value per sample -- one for the whole batch when it is a learnt constant; poisson: per pixel)
                 a.noise_n = self.noise_std.numel() if self.style == "poisson" else (1 if self.mode == "const" else self.B)
             else:
                 a.out = _ptr(self.main.tensor("out32"))
