@@ -2,29 +2,22 @@
 // forward AND hand-derived backward, fp32 (gfx950).  Replaces Denoiser._ssdn_pipeline / _mse_pipeline /
 // _mask_mse_pipeline (/root/reference/ssdn/ssdn/denoiser.py:140-397, utils/n2v_loss.py:6-17) and their autograd graphs.
 // The math (closed-form 3x3 SPD algebra and its derivative) is documented in DESIGN.md section "posterior head".
-#include "head_common.h"
+// The sigma rule, the softplus'd estimate, Sigma_x = U U^T, dL/dU = 2 G U, the pixel range and the keep rule are head_math.h's, shared
+// with head_impulse.hip; so is the adjugate (sym3_adj) where it left the generated code alone: the posterior-mean terms of k_head_vjp
+// and head_dy_pixel.
+// k_head and k_head_vjp keep one arm per head kind (full C = 1, full C = 3, diagonal) inside their pixel loops, and four adjugates stay
+// spelled out: this file is compiled with floating-point contraction on, and with the arms moved into per-pixel functions of their own
+// (even word for word) or those adjugates routed through sym3_adj the compiler vectorised and contracted the arithmetic differently, or
+// spilled more registers.  The kernels' results are kept bit for bit.
+#include "head_math.h"
 
+static constexpr float PME_EPS = 1e-6f;        // the reference's regulariser of the posterior mean's inverses
 // ---- DIAGONAL_COVARIANCE: C = 3, net_out = [mu_0..2, a_0..2], Sigma_x = diag(a_c^2).  Every quantity is per
 // channel: sy_c = a_c^2 + sigma_c^2, no adjugate.  (C = 1 is the same model with or without the flag: its runs use the DIAG = false code.)
-// sigma_c of one channel (k_head's rules) and its derivatives by mu_c and by the softplus'd estimate
-static __device__ __forceinline__ void diag_sigma(int style, int mode, float npar, float est, float mu, float& sig, float& dsig_dmu,
-                                                  float& dsig_dest) {
-    if (style == 0) {
-        sig = mode == 0 ? fmaxf(npar, 1e-3f) : est;
-        dsig_dmu = 0.f;
-        dsig_dest = 1.f;
-    } else {
-        float m = fmaxf(mu, 1e-3f);
-        float f = mode == 0 ? 1.f / npar : est;
-        sig = sqrtf(m * f);
-        dsig_dmu = mu > 1e-3f ? 0.5f * f / sig : 0.f;
-        dsig_dest = 0.5f * m / sig;
-    }
-}
 // posterior mean of one channel, the reference's three eps-regularised inverses written for diagonal matrices:
 //   pme = (mu ix + y in) / (ix + in + eps) = mu u + y v,   ix = 1/(sx + eps), in = 1/(sn + eps), u = ix rD, v = in rD, rD = 1/(ix + in + eps)
 static __device__ __forceinline__ float diag_pme_weights(float sx, float sn, float& ix, float& in, float& u, float& v) {
-    const float e = 1e-6f;
+    const float e = PME_EPS;
     ix = 1.f / (sx + e);
     in = 1.f / (sn + e);
     const float rD = 1.f / (ix + in + e);
@@ -33,6 +26,12 @@ static __device__ __forceinline__ float diag_pme_weights(float sx, float sn, flo
     return rD;
 }
 
+// posterior mean (denoiser.py:366-372) in its algebraically equal, well-conditioned form
+//   (Sx'^-1 + Sn'^-1)^-1 (Sx'^-1 mu + Sn'^-1 y) = mu + Sx' T^-1 (y - mu),  Sx' = Sx + eps I, Sn' = Sn + eps I, T = Sx' + Sn' = Sy + 2 eps I
+// adj T into k; returns 1 / det T
+static __device__ __forceinline__ float gauss3_pme_adj(const Sym3& s, Sym3& k) {
+    return 1.f / sym3_adj(sym3_add_diag(s, 2 * PME_EPS, 2 * PME_EPS, 2 * PME_EPS), k);
+}
 template <bool DIAG>
 __global__ void k_head(ssdn_head_args a) {
     __shared__ float sh[4];
@@ -41,17 +40,12 @@ __global__ void k_head(ssdn_head_args a) {
     const int C = a.C;
     const int Cout = DIAG ? 2 * C : C + C * (C + 1) / 2;
     const float inv_total = 1.f / ((float)a.B * (float)HW);  // mean over pixels, then mean over the batch
-    float est = 0.f, dest_draw = 0.f;
-    if (a.mode != 0) {
-        float raw = a.est_raw[a.mode == 2 ? b : 0];
-        est = softplus_m4(raw);
-        dest_draw = sigmoid_m4(raw);
-    }
+    const HeadEst he = head_est(a.mode, a.est_raw, b);
+    const float est = he.est, dest_draw = he.dest_draw;
     const float npar = a.noise_param ? a.noise_param[b] : 0.f;
     float loss_acc = 0.f, gest_acc = 0.f, gabs = 0.f;
-    const long long per = (HW + a.nchunks - 1) / a.nchunks;
-    const long long p0 = (long long)blockIdx.x * per;
-    const long long p1 = p0 + per < HW ? p0 + per : HW;
+    const HeadRange r = head_range(HW, a.nchunks);
+    const long long p0 = r.p0, p1 = r.p1;
     const float* no = a.net_out + (long long)b * Cout * HW;
     const float* ny = a.noisy + (long long)b * C * HW;
     for (long long p = p0 + threadIdx.x; p < p1; p += HB) {
@@ -63,7 +57,7 @@ __global__ void k_head(ssdn_head_args a) {
             for (int c = 0; c < 3; ++c) {
                 mu[c] = no[c * HW + p];
                 av[c] = no[(3 + c) * HW + p];
-                diag_sigma(a.style, a.mode, npar, est, mu[c], sig[c], dsig_dmu[c], dsig_dest[c]);
+                head_sigma(a.style, a.mode, npar, est, mu[c], sig[c], dsig_dmu[c], dsig_dest[c]);
                 sx[c] = av[c] * av[c];
                 sn[c] = sig[c] * sig[c];
                 const float sy = sx[c] + sn[c], d = ny[c * HW + p] - mu[c];
@@ -107,17 +101,8 @@ __global__ void k_head(ssdn_head_args a) {
             }
         } else if (C == 1) {
             float mu = no[p], av = no[HW + p], y = ny[p];
-            float sig, dsig_dmu = 0.f, dsig_dest = 0.f;
-            if (a.style == 0) {
-                sig = a.mode == 0 ? fmaxf(npar, 1e-3f) : est;
-                dsig_dest = 1.f;
-            } else {
-                float m = fmaxf(mu, 1e-3f);
-                float f = a.mode == 0 ? 1.f / npar : est;
-                sig = sqrtf(m * f);
-                dsig_dmu = mu > 1e-3f ? 0.5f * f / sig : 0.f;
-                dsig_dest = 0.5f * m / sig;
-            }
+            float sig, dsig_dmu, dsig_dest;
+            head_sigma(a.style, a.mode, npar, est, mu, sig, dsig_dmu, dsig_dest);
             float sx = av * av, sn = sig * sig, sy = sx + sn;
             float d = y - mu;
             float l = d * d / sy + logf(sy);
@@ -144,35 +129,19 @@ __global__ void k_head(ssdn_head_args a) {
 #pragma unroll
             for (int c = 0; c < 6; ++c) A[c] = no[(3 + c) * HW + p];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                if (a.style == 0) {
-                    sig[c] = a.mode == 0 ? fmaxf(npar, 1e-3f) : est;
-                    dsig_dmu[c] = 0.f;
-                    dsig_dest[c] = 1.f;
-                } else {
-                    float m = fmaxf(mu[c], 1e-3f);
-                    float f = a.mode == 0 ? 1.f / npar : est;
-                    sig[c] = sqrtf(m * f);
-                    dsig_dmu[c] = mu[c] > 1e-3f ? 0.5f * f / sig[c] : 0.f;
-                    dsig_dest[c] = 0.5f * m / sig[c];
-                }
-            }
-            // Sigma_x = U U^T, U = [[a0,a1,a2],[0,a3,a4],[0,0,a5]]   (denoiser.py:246-255)
-            float x00 = A[0] * A[0] + A[1] * A[1] + A[2] * A[2];
-            float x01 = A[1] * A[3] + A[2] * A[4];
-            float x02 = A[2] * A[5];
-            float x11 = A[3] * A[3] + A[4] * A[4];
-            float x12 = A[4] * A[5];
-            float x22 = A[5] * A[5];
+            for (int c = 0; c < 3; ++c) head_sigma(a.style, a.mode, npar, est, mu[c], sig[c], dsig_dmu[c], dsig_dest[c]);
+            const Sym3 x = sym3_uut(A);
+            const float x00 = x.m00, x01 = x.m01, x02 = x.m02, x11 = x.m11, x12 = x.m12, x22 = x.m22;
             float n0 = sig[0] * sig[0], n1 = sig[1] * sig[1], n2 = sig[2] * sig[2];
             float s00 = x00 + n0, s01 = x01, s02 = x02, s11 = x11 + n1, s12 = x12, s22 = x22 + n2;
-            // adjugate / determinant of the SPD 3x3 Sigma_y
+            float d0 = y[0] - mu[0], d1 = y[1] - mu[1], d2 = y[2] - mu[2];
+            // adjugate / determinant of the SPD 3x3 Sigma_y, here and for T below spelled out: through sym3_adj (head_math.h) this kernel
+            // spilled two more VGPRs
             float c00 = s11 * s22 - s12 * s12, c01 = s02 * s12 - s01 * s22, c02 = s01 * s12 - s02 * s11;
             float c11 = s00 * s22 - s02 * s02, c12 = s01 * s02 - s00 * s12, c22 = s00 * s11 - s01 * s01;
             float det = s00 * c00 + s01 * c01 + s02 * c02;
             float rdet = 1.f / det;
             float i00 = c00 * rdet, i01 = c01 * rdet, i02 = c02 * rdet, i11 = c11 * rdet, i12 = c12 * rdet, i22 = c22 * rdet;
-            float d0 = y[0] - mu[0], d1 = y[1] - mu[1], d2 = y[2] - mu[2];
             float q0 = i00 * d0 + i01 * d1 + i02 * d2;
             float q1 = i01 * d0 + i11 * d1 + i12 * d2;
             float q2 = i02 * d0 + i12 * d1 + i22 * d2;
@@ -184,9 +153,7 @@ __global__ void k_head(ssdn_head_args a) {
             long long o3 = (long long)b * 3 * HW + p;
             if (a.mu) { a.mu[o3] = mu[0]; a.mu[o3 + HW] = mu[1]; a.mu[o3 + 2 * HW] = mu[2]; }
             if (a.pme) {
-                // posterior mean (denoiser.py:366-372) in its algebraically equal, well-conditioned form
-                //   (Sx'^-1 + Sn'^-1)^-1 (Sx'^-1 mu + Sn'^-1 y) = mu + Sx' (Sx' + Sn')^-1 (y - mu),  Sx' = Sx + eps I, Sn' = Sn + eps I
-                const float e = 1e-6f;
+                const float e = PME_EPS;
                 float t00 = s00 + 2 * e, t11 = s11 + 2 * e, t22 = s22 + 2 * e;
                 float k00 = t11 * t22 - s12 * s12, k01 = s02 * s12 - s01 * t22, k02 = s01 * s12 - s02 * t11;
                 float k11 = t00 * t22 - s02 * s02, k12 = s01 * s02 - t00 * s12, k22 = t00 * t11 - s01 * s01;
@@ -203,21 +170,15 @@ __global__ void k_head(ssdn_head_args a) {
             if (a.want_grad) {
                 // G = dl/dSigma_y = 1/2 Sy^-1 [det>0] - 1/2 q q^T
                 float hd = det > 0.f ? 0.5f : 0.f;
-                float g00 = hd * i00 - 0.5f * q0 * q0, g01 = hd * i01 - 0.5f * q0 * q1, g02 = hd * i02 - 0.5f * q0 * q2;
-                float g11 = hd * i11 - 0.5f * q1 * q1, g12 = hd * i12 - 0.5f * q1 * q2, g22 = hd * i22 - 0.5f * q2 * q2;
+                const Sym3 G = {hd * i00 - 0.5f * q0 * q0, hd * i01 - 0.5f * q0 * q1, hd * i02 - 0.5f * q0 * q2,
+                                hd * i11 - 0.5f * q1 * q1, hd * i12 - 0.5f * q1 * q2, hd * i22 - 0.5f * q2 * q2};
                 float reg = a.mode != 0 ? 0.1f / 3.f : 0.f;
-                float ds0 = 2.f * sig[0] * g00 - reg, ds1 = 2.f * sig[1] * g11 - reg, ds2 = 2.f * sig[2] * g22 - reg;
+                float ds0 = 2.f * sig[0] * G.m00 - reg, ds1 = 2.f * sig[1] * G.m11 - reg, ds2 = 2.f * sig[2] * G.m22 - reg;
                 float g[9];
                 g[0] = -q0 + ds0 * dsig_dmu[0];
                 g[1] = -q1 + ds1 * dsig_dmu[1];
                 g[2] = -q2 + ds2 * dsig_dmu[2];
-                // dl/dU = 2 G U on the upper triangle
-                g[3] = 2.f * (g00 * A[0]);
-                g[4] = 2.f * (g00 * A[1] + g01 * A[3]);
-                g[5] = 2.f * (g00 * A[2] + g01 * A[4] + g02 * A[5]);
-                g[6] = 2.f * (g01 * A[1] + g11 * A[3]);
-                g[7] = 2.f * (g01 * A[2] + g11 * A[4] + g12 * A[5]);
-                g[8] = 2.f * (g02 * A[2] + g12 * A[4] + g22 * A[5]);
+                sym3_dldu(G, A, g + 3);
 #pragma unroll
                 for (int c = 0; c < 9; ++c) {
                     float v = g[c] * inv_total;
@@ -237,19 +198,31 @@ __global__ void k_head(ssdn_head_args a) {
     }
     if (a.want_grad && a.gmax) atomic_max_abs_block(a.gmax, gabs, sh);
     if (blockIdx.x == 0 && threadIdx.x == 0 && a.noise_std && a.style == 0)
-        a.noise_std[b] = a.mode == 0 ? fmaxf(npar, 1e-3f) : est;
+        a.noise_std[b] = head_sigma(0, a.mode, npar, est, 0.f);
+}
+// the argument rules of SSDN_OP_HEAD_SSDN and SSDN_OP_HEAD_VJP (the structs share these fields), every style; op: the error text's prefix
+template <class Args>
+static int check_head_args(const char* op, const Args* a, bool need_g) {
+    if (a->diag && a->C != 1 && a->C != 3) return ssdn_set_error("%s: diag needs C = 1 or 3", op);
+    if (a->C != 1 && a->C != 3) return ssdn_set_error("%s: C must be 1 or 3 (denoiser.py:199)", op);
+    if (a->diag != 0 && a->diag != 1) return ssdn_set_error("%s: diag must be 0 or 1", op);
+    if (a->B < 1 || a->H < 1 || a->W < 1 || a->nchunks < 1) return ssdn_set_error("%s: bad shape", op);
+    if (a->mode < 0 || a->mode > 2 || a->style < 0 || a->style > 2) return ssdn_set_error("%s: bad style / mode", op);
+    if (!a->net_out || !a->noisy || !a->partial) return ssdn_set_error("%s: net_out, noisy and partial must be given", op);
+    if (need_g && !a->g_net_out) return ssdn_set_error("%s: g_net_out must be given", op);
+    if (a->mode == 0 && !a->noise_param) return ssdn_set_error("%s: mode known needs noise_param", op);
+    if (a->mode != 0 && !a->est_raw) return ssdn_set_error("%s: modes const / var need est_raw", op);
+    return 0;
 }
 int launch_head(const ssdn_head_args* a, hipStream_t s) {
-    if (a->diag && a->C != 1 && a->C != 3) return ssdn_set_error("head: diag needs C = 1 or 3");
-    if (a->C != 1 && a->C != 3) return ssdn_set_error("head: C must be 1 or 3 (denoiser.py:199)");
-    if (a->diag != 0 && a->diag != 1) return ssdn_set_error("head: diag must be 0 or 1");
-    if (a->nchunks < 1) return ssdn_set_error("head: nchunks < 1");
+    if (int rc = check_head_args("head", a, a->want_grad != 0)) return rc;
     if (a->style == 2) return launch_head_impulse(a, s);          // head_impulse.hip
     if (a->diag && a->C == 3) hipLaunchKernelGGL(k_head<true>, dim3(a->nchunks, a->B), dim3(HB), 0, s, *a);
     else hipLaunchKernelGGL(k_head<false>, dim3(a->nchunks, a->B), dim3(HB), 0, s, *a);
     return 0;
 }
 
+// loss[b] (where asked for: the vector-Jacobian product passes loss = NULL) and g_est from the partials
 __global__ void k_head_final(ssdn_head_final_args a) {
     // one thread per sample sums that sample's partials in index order (deterministic)
     int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -260,7 +233,7 @@ __global__ void k_head_final(ssdn_head_final_args a) {
             l += a.partial[((long long)b * a.nchunks + c) * 2];
             g += a.partial[((long long)b * a.nchunks + c) * 2 + 1];
         }
-        a.loss[b] = l / (float)HW;
+        if (a.loss) a.loss[b] = l / (float)HW;
         if (a.mode == 2 && a.g_est) a.g_est[b] = g;
     }
     if (a.mode == 1 && a.g_est && b == 0) {
@@ -494,15 +467,13 @@ int launch_metrics(const ssdn_metrics_args* a, hipStream_t s) {
 // ---- SSDN_OP_HEAD_VJP / SSDN_OP_MSE_VJP: the pipelines' vector-Jacobian products for any upstream gradient ------------------------
 // (Denoiser.run_pipeline under autograd: dL/dLOSS = w, dL/dIMG_DENOISED = g_pme, dL/dIMG_MU = g_mu; math in DESIGN.md section 3.8.)
 // dL/dnoisy of the head at pixel p of one sample, net_out and sigma held fixed.  LOSS: C = 1, l = d^2/sy + log sy:
-// 2 sc d/sy; C = 3, l = 1/2 d^T Sy^-1 d + 1/2 log det Sy: sc Sy^-1 d (Sy as k_head inverts it).  Posterior mean: C = 1, (y sx + mu sn)/sy:
+// 2 sc d/sy; C = 3, l = 1/2 d^T Sy^-1 d + 1/2 log det Sy: sc Sy^-1 d (adjugate over determinant).  Posterior mean: C = 1, (y sx + mu sn)/sy:
 // g sx/sy; C = 3, mu + S' T^-1 d: h = T^-1 S' g.  IMG_MU does not read the noisy image.
 static __device__ __forceinline__ void head_dy_pixel(const ssdn_head_vjp_args& a, const float* no, const float* ny, const float* gp, float* gy,
                                                      long long p, long long HW, float sc, float npar, float est) {
     if (a.C == 1) {
         float mu = no[p], av = no[HW + p], y = ny[p];
-        float sig;
-        if (a.style == 0) sig = a.mode == 0 ? fmaxf(npar, 1e-3f) : est;
-        else sig = sqrtf(fmaxf(mu, 1e-3f) * (a.mode == 0 ? 1.f / npar : est));
+        float sig = head_sigma(a.style, a.mode, npar, est, mu);
         float sx = av * av, sy = sx + sig * sig, rs = 1.f / sy, d = y - mu;
         float v = sc != 0.f ? 2.f * d * rs * sc : 0.f;
         if (gp) v += gp[p] * sx * rs;
@@ -515,43 +486,33 @@ static __device__ __forceinline__ void head_dy_pixel(const ssdn_head_vjp_args& a
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         mu[c] = no[c * HW + p];
-        float sig;
-        if (a.style == 0) sig = a.mode == 0 ? fmaxf(npar, 1e-3f) : est;
-        else sig = sqrtf(fmaxf(mu[c], 1e-3f) * (a.mode == 0 ? 1.f / npar : est));
+        float sig = head_sigma(a.style, a.mode, npar, est, mu[c]);
         n[c] = sig * sig;
     }
-    float x00 = A[0] * A[0] + A[1] * A[1] + A[2] * A[2];
-    float x01 = A[1] * A[3] + A[2] * A[4];
-    float x02 = A[2] * A[5];
-    float x11 = A[3] * A[3] + A[4] * A[4];
-    float x12 = A[4] * A[5];
-    float x22 = A[5] * A[5];
+    const Sym3 x = sym3_uut(A);
+    const float x00 = x.m00, x01 = x.m01, x02 = x.m02, x11 = x.m11, x12 = x.m12, x22 = x.m22;
     float s00 = x00 + n[0], s11 = x11 + n[1], s22 = x22 + n[2];
     float d0 = ny[p] - mu[0], d1 = ny[HW + p] - mu[1], d2 = ny[2 * HW + p] - mu[2];
-    float v0 = 0.f, v1 = 0.f, v2 = 0.f;
-    if (sc != 0.f) {                    // sc Sy^-1 d (adjugate over determinant, as the forward)
+    float v[3] = {0.f, 0.f, 0.f};
+    if (sc != 0.f) {                    // sc Sy^-1 d (spelled out like the LOSS term of k_head_vjp's C = 3 arm, for the same reason)
         float c00 = s11 * s22 - x12 * x12, c01 = x02 * x12 - x01 * s22, c02 = x01 * x12 - x02 * s11;
         float c11 = s00 * s22 - x02 * x02, c12 = x01 * x02 - s00 * x12, c22 = s00 * s11 - x01 * x01;
         float rdet = 1.f / (s00 * c00 + x01 * c01 + x02 * c02);
-        v0 = (c00 * d0 + c01 * d1 + c02 * d2) * rdet * sc;
-        v1 = (c01 * d0 + c11 * d1 + c12 * d2) * rdet * sc;
-        v2 = (c02 * d0 + c12 * d1 + c22 * d2) * rdet * sc;
+        v[0] = (c00 * d0 + c01 * d1 + c02 * d2) * rdet * sc;
+        v[1] = (c01 * d0 + c11 * d1 + c12 * d2) * rdet * sc;
+        v[2] = (c02 * d0 + c12 * d1 + c22 * d2) * rdet * sc;
     }
     if (gp) {                           // h = T^-1 S' g, S' = Sx + eps I, T = Sy + 2 eps I
-        const float e = 1e-6f;
-        float ga0 = gp[p], ga1 = gp[HW + p], ga2 = gp[2 * HW + p];
-        float t00 = s00 + 2 * e, t11 = s11 + 2 * e, t22 = s22 + 2 * e;
-        float k00 = t11 * t22 - x12 * x12, k01 = x02 * x12 - x01 * t22, k02 = x01 * x12 - x02 * t11;
-        float k11 = t00 * t22 - x02 * x02, k12 = x01 * x02 - t00 * x12, k22 = t00 * t11 - x01 * x01;
-        float rd = 1.f / (t00 * k00 + x01 * k01 + x02 * k02);
-        float u0 = (x00 + e) * ga0 + x01 * ga1 + x02 * ga2;
-        float u1 = x01 * ga0 + (x11 + e) * ga1 + x12 * ga2;
-        float u2 = x02 * ga0 + x12 * ga1 + (x22 + e) * ga2;
-        v0 += (k00 * u0 + k01 * u1 + k02 * u2) * rd;
-        v1 += (k01 * u0 + k11 * u1 + k12 * u2) * rd;
-        v2 += (k02 * u0 + k12 * u1 + k22 * u2) * rd;
+        const Sym3 s = {s00, x01, x02, s11, x12, s22};
+        const float ga[3] = {gp[p], gp[HW + p], gp[2 * HW + p]};
+        Sym3 k;
+        float u[3], h[3];
+        const float rd = gauss3_pme_adj(s, k);
+        sym3_mv(sym3_add_diag(x, PME_EPS, PME_EPS, PME_EPS), ga, 1.f, u);
+        sym3_mv(k, u, rd, h);
+        v[0] += h[0]; v[1] += h[1]; v[2] += h[2];
     }
-    gy[p] = v0; gy[HW + p] = v1; gy[2 * HW + p] = v2;
+    gy[p] = v[0]; gy[HW + p] = v[1]; gy[2 * HW + p] = v[2];
 }
 // DIAG: per channel, LOSS sc d_c/sy_c, posterior mean g_c v_c (v_c = in_c / (ix_c + in_c + eps), diag_pme_weights)
 static __device__ __forceinline__ void head_dy_pixel_diag(const ssdn_head_vjp_args& a, const float* no, const float* ny, const float* gp,
@@ -559,8 +520,7 @@ static __device__ __forceinline__ void head_dy_pixel_diag(const ssdn_head_vjp_ar
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         float mu = no[c * HW + p], av = no[(3 + c) * HW + p];
-        float sig, dsig_dmu, dsig_dest;
-        diag_sigma(a.style, a.mode, npar, est, mu, sig, dsig_dmu, dsig_dest);
+        float sig = head_sigma(a.style, a.mode, npar, est, mu);
         float sx = av * av, sn = sig * sig;
         float v = sc != 0.f ? (ny[c * HW + p] - mu) / (sx + sn) * sc : 0.f;
         if (gp) {
@@ -587,21 +547,16 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, GY ? HB : 1024))) void 
     const int C = a.C;
     const int Cout = DIAG ? 2 * C : C + C * (C + 1) / 2;
     const float wb = a.w ? a.w[b] : 0.f;
-    const bool skip = a.keep && !a.g_pme && !a.g_mu && a.w && wb == 1.f / (float)a.B;
+    const bool skip = head_vjp_kept(a.keep, a.g_pme, a.g_mu, a.w, wb, a.B);
     if (skip && !GY) return;                         // (block-uniform: before any barrier)
     const float sc = wb / (float)HW;        // LOSS[b] is the mean over the pixels of sample b
-    float est = 0.f, dest_draw = 0.f;
-    if (a.mode != 0) {
-        float raw = a.est_raw[a.mode == 2 ? b : 0];
-        est = softplus_m4(raw);
-        dest_draw = sigmoid_m4(raw);
-    }
+    const HeadEst he = head_est(a.mode, a.est_raw, b);
+    const float est = he.est, dest_draw = he.dest_draw;
     const float npar = a.noise_param ? a.noise_param[b] : 0.f;
     const float reg = a.mode != 0 ? 0.1f : 0.f;
     float gest_acc = 0.f, gabs = 0.f;
-    const long long per = (HW + a.nchunks - 1) / a.nchunks;
-    const long long p0 = (long long)blockIdx.x * per;
-    const long long p1 = p0 + per < HW ? p0 + per : HW;
+    const HeadRange r = head_range(HW, a.nchunks);
+    const long long p0 = r.p0, p1 = r.p1;
     const float* no = a.net_out + (long long)b * Cout * HW;
     const float* ny = a.noisy + (long long)b * C * HW;
     const float* gp = a.g_pme ? a.g_pme + (long long)b * C * HW : nullptr;
@@ -618,7 +573,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, GY ? HB : 1024))) void 
                 mu[c] = no[c * HW + p];
                 av[c] = no[(3 + c) * HW + p];
                 y[c] = ny[c * HW + p];
-                diag_sigma(a.style, a.mode, npar, est, mu[c], sig[c], dsig_dmu[c], dsig_dest[c]);
+                head_sigma(a.style, a.mode, npar, est, mu[c], sig[c], dsig_dmu[c], dsig_dest[c]);
                 sx[c] = av[c] * av[c];
                 sn[c] = sig[c] * sig[c];
                 prod *= sx[c] + sn[c];
@@ -661,17 +616,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, GY ? HB : 1024))) void 
             gest_acc += gs;
         } else if (C == 1) {
             float mu = no[p], av = no[HW + p], y = ny[p];
-            float sig, dsig_dmu = 0.f, dsig_dest = 0.f;
-            if (a.style == 0) {
-                sig = a.mode == 0 ? fmaxf(npar, 1e-3f) : est;
-                dsig_dest = 1.f;
-            } else {
-                float m = fmaxf(mu, 1e-3f);
-                float f = a.mode == 0 ? 1.f / npar : est;
-                sig = sqrtf(m * f);
-                dsig_dmu = mu > 1e-3f ? 0.5f * f / sig : 0.f;
-                dsig_dest = 0.5f * m / sig;
-            }
+            float sig, dsig_dmu, dsig_dest;
+            head_sigma(a.style, a.mode, npar, est, mu, sig, dsig_dmu, dsig_dest);
             float sx = av * av, sn = sig * sig, sy = sx + sn;
             float d = y - mu;
             float dmu = 0.f, dsx = 0.f, dsn = 0.f, dsig = 0.f;
@@ -703,33 +649,19 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, GY ? HB : 1024))) void 
 #pragma unroll
             for (int c = 0; c < 6; ++c) A[c] = no[(3 + c) * HW + p];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                if (a.style == 0) {
-                    sig[c] = a.mode == 0 ? fmaxf(npar, 1e-3f) : est;
-                    dsig_dmu[c] = 0.f;
-                    dsig_dest[c] = 1.f;
-                } else {
-                    float m = fmaxf(mu[c], 1e-3f);
-                    float f = a.mode == 0 ? 1.f / npar : est;
-                    sig[c] = sqrtf(m * f);
-                    dsig_dmu[c] = mu[c] > 1e-3f ? 0.5f * f / sig[c] : 0.f;
-                    dsig_dest[c] = 0.5f * m / sig[c];
-                }
-            }
-            float x00 = A[0] * A[0] + A[1] * A[1] + A[2] * A[2];
-            float x01 = A[1] * A[3] + A[2] * A[4];
-            float x02 = A[2] * A[5];
-            float x11 = A[3] * A[3] + A[4] * A[4];
-            float x12 = A[4] * A[5];
-            float x22 = A[5] * A[5];
-            float n0 = sig[0] * sig[0], n1 = sig[1] * sig[1], n2 = sig[2] * sig[2];
-            float s00 = x00 + n0, s01 = x01, s02 = x02, s11 = x11 + n1, s12 = x12, s22 = x22 + n2;
-            float d0 = y[0] - mu[0], d1 = y[1] - mu[1], d2 = y[2] - mu[2];
-            // G: dL/dSigma_x as a symmetric matrix (dL/dx01 as a scalar = 2 G01, the convention of k_head's G U map);
+            for (int c = 0; c < 3; ++c) head_sigma(a.style, a.mode, npar, est, mu[c], sig[c], dsig_dmu[c], dsig_dest[c]);
+            const Sym3 x = sym3_uut(A);
+            const Sym3 s = sym3_add_diag(x, sig[0] * sig[0], sig[1] * sig[1], sig[2] * sig[2]);
+            const float d[3] = {y[0] - mu[0], y[1] - mu[1], y[2] - mu[2]};
+            const float x00 = x.m00, x01 = x.m01, x02 = x.m02, x11 = x.m11, x12 = x.m12, x22 = x.m22;
+            const float s00 = s.m00, s01 = s.m01, s02 = s.m02, s11 = s.m11, s12 = s.m12, s22 = s.m22;
+            const float d0 = d[0], d1 = d[1], d2 = d[2];
+            // G: dL/dSigma_x as a symmetric matrix (dL/dx01 as a scalar = 2 G01, the convention of sym3_dldu);
             // dn: dL/d(sigma_c^2); gmu: dL/dmu without the sigma chain
             float g00 = 0.f, g01 = 0.f, g02 = 0.f, g11 = 0.f, g12 = 0.f, g22 = 0.f;
             float dn0 = 0.f, dn1 = 0.f, dn2 = 0.f, gmu0 = 0.f, gmu1 = 0.f, gmu2 = 0.f, rg = 0.f;
             if (sc != 0.f) {            // LOSS: 1/2 log det Sy + 1/2 d^T Sy^-1 d (- 0.1 mean sig); G = 1/2 Sy^-1 [det>0] - 1/2 q q^T
+                // (this adjugate stays spelled out: through sym3_adj the compiler contracted this kernel's arithmetic differently)
                 float c00 = s11 * s22 - s12 * s12, c01 = s02 * s12 - s01 * s22, c02 = s01 * s12 - s02 * s11;
                 float c11 = s00 * s22 - s02 * s02, c12 = s01 * s02 - s00 * s12, c22 = s00 * s11 - s01 * s01;
                 float det = s00 * c00 + s01 * c01 + s02 * c02;
@@ -746,12 +678,11 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, GY ? HB : 1024))) void 
                 rg = reg * (1.f / 3.f) * sc;
             }
             if (gp) {                   // posterior mean mu + S' T^-1 d, S' = Sx + eps I, T = Sy + 2 eps I (the forward's form)
-                const float e = 1e-6f;
+                const float e = PME_EPS;
                 float ga0 = gp[p], ga1 = gp[HW + p], ga2 = gp[2 * HW + p];
-                float t00 = s00 + 2 * e, t11 = s11 + 2 * e, t22 = s22 + 2 * e;
-                float k00 = t11 * t22 - s12 * s12, k01 = s02 * s12 - s01 * t22, k02 = s01 * s12 - s02 * t11;
-                float k11 = t00 * t22 - s02 * s02, k12 = s01 * s02 - t00 * s12, k22 = t00 * t11 - s01 * s01;
-                float rd = 1.f / (t00 * k00 + s01 * k01 + s02 * k02);
+                Sym3 kk;
+                float rd = gauss3_pme_adj(s, kk);
+                const float k00 = kk.m00, k01 = kk.m01, k02 = kk.m02, k11 = kk.m11, k12 = kk.m12, k22 = kk.m22;
                 float r0 = (k00 * d0 + k01 * d1 + k02 * d2) * rd;
                 float r1 = (k01 * d0 + k11 * d1 + k12 * d2) * rd;
                 float r2 = (k02 * d0 + k12 * d1 + k22 * d2) * rd;
@@ -774,12 +705,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, GY ? HB : 1024))) void 
             g[0] = gmu0 + ds0 * dsig_dmu[0] + (gm ? gm[p] : 0.f);
             g[1] = gmu1 + ds1 * dsig_dmu[1] + (gm ? gm[HW + p] : 0.f);
             g[2] = gmu2 + ds2 * dsig_dmu[2] + (gm ? gm[2 * HW + p] : 0.f);
-            g[3] = 2.f * (g00 * A[0]);
-            g[4] = 2.f * (g00 * A[1] + g01 * A[3]);
-            g[5] = 2.f * (g00 * A[2] + g01 * A[4] + g02 * A[5]);
-            g[6] = 2.f * (g01 * A[1] + g11 * A[3]);
-            g[7] = 2.f * (g01 * A[2] + g11 * A[4] + g12 * A[5]);
-            g[8] = 2.f * (g02 * A[2] + g12 * A[4] + g22 * A[5]);
+            { const Sym3 G = {g00, g01, g02, g11, g12, g22}; sym3_dldu(G, A, g + 3); }
 #pragma unroll
             for (int c = 0; c < 9; ++c) {
                 go[c * HW + p] = g[c];
@@ -800,30 +726,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, GY ? HB : 1024))) void 
     if (threadIdx.x == 0) a.partial[((long long)b * a.nchunks + blockIdx.x) * 2 + 1] = gs * dest_draw;
     if (a.gmax) atomic_max_abs_block(a.gmax, gabs, sh);
 }
-// g_est from the partials in k_head_final's order (skipped samples' partials are the forward's: the sum is too); the loss sums untouched
-__global__ void k_head_vjp_final(ssdn_head_vjp_args a) {
-    int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < a.B && a.mode == 2) {
-        float g = 0.f;
-        for (int c = 0; c < a.nchunks; ++c) g += a.partial[((long long)b * a.nchunks + c) * 2 + 1];
-        a.g_est[b] = g;
-    }
-    if (a.mode == 1 && b == 0) {
-        float g = 0.f;
-        for (int bb = 0; bb < a.B; ++bb)
-            for (int c = 0; c < a.nchunks; ++c) g += a.partial[((long long)bb * a.nchunks + c) * 2 + 1];
-        a.g_est[0] = g;
-    }
-}
 int launch_head_vjp(const ssdn_head_vjp_args* a, hipStream_t s) {
-    if (a->diag && a->C != 1 && a->C != 3) return ssdn_set_error("head_vjp: diag needs C = 1 or 3");
-    if (a->C != 1 && a->C != 3) return ssdn_set_error("head_vjp: C must be 1 or 3");
-    if (a->diag != 0 && a->diag != 1) return ssdn_set_error("head_vjp: diag must be 0 or 1");
-    if (a->B < 1 || a->H < 1 || a->W < 1 || a->nchunks < 1) return ssdn_set_error("head_vjp: bad shape");
-    if (a->mode < 0 || a->mode > 2 || a->style < 0 || a->style > 2) return ssdn_set_error("head_vjp: bad style / mode");
-    if (!a->net_out || !a->noisy || !a->g_net_out || !a->partial) return ssdn_set_error("head_vjp: net_out, noisy, g_net_out and partial must be given");
-    if (a->mode == 0 && !a->noise_param) return ssdn_set_error("head_vjp: mode known needs noise_param");
-    if (a->mode != 0 && !a->est_raw) return ssdn_set_error("head_vjp: modes const / var need est_raw");
+    if (int rc = check_head_args("head_vjp", a, true)) return rc;
     const dim3 grid(a->nchunks, a->B);
     if (a->style == 2) {                                             // head_impulse.hip; the reductions below serve it unchanged
         if (int rc = launch_head_vjp_impulse(a, s)) return rc;
@@ -833,12 +737,9 @@ int launch_head_vjp(const ssdn_head_vjp_args* a, hipStream_t s) {
     } else if (a->g_noisy) hipLaunchKernelGGL((k_head_vjp<true, false>), grid, dim3(HB), 0, s, *a);
     else hipLaunchKernelGGL((k_head_vjp<false, false>), grid, dim3(HB), 0, s, *a);
     if (a->mode != 0 && a->g_est) {
-        hipLaunchKernelGGL(k_head_vjp_final, dim3((a->B + 63) / 64), dim3(64), 0, s, *a);
-        if (a->mode == 2 && a->g_sigma_out) {
-            ssdn_head_final_args f = {a->partial, a->B, a->nchunks, a->H, a->W, a->mode, nullptr, a->g_est, a->g_sigma_out, a->gmax2};
-            long long n = (long long)a->B * a->H * a->W;
-            hipLaunchKernelGGL(k_fill_sigma_grad, dim3((int)((n + 255) / 256)), dim3(256), 0, s, f);
-        }
+        // g_est from the partials in the forward's order (kept samples' partials are the forward's: the sum is too); no loss store
+        const ssdn_head_final_args f = {a->partial, a->B, a->nchunks, a->H, a->W, a->mode, nullptr, a->g_est, a->g_sigma_out, a->gmax2};
+        return launch_head_final(&f, s);
     }
     return 0;
 }

@@ -1,31 +1,20 @@
 // head_impulse.hip -- the loss head of the IMPULSE noise model (style 2; Laine et al.'s third corruption model), forward and
 // vector-Jacobian product, fp32 (gfx950).  With probability alpha a pixel is replaced, in all channels, by a colour drawn uniformly
-// from [0,1)^C; otherwise it is left alone.  Per pixel, with mu_x, Sigma_x = U U^T from net_out as in k_head and e = mu_x - 1/2:
+// from [0,1)^C; otherwise it is left alone.  Per pixel, with mu_x, Sigma_x = U U^T from net_out (sym3_uut) and e = mu_x - 1/2:
 //   training loss: the Gaussian moment match of the mixture,
 //     mu_y = alpha/2 + (1 - alpha) mu_x,   Sigma_y = (1 - alpha) Sigma_x + alpha/12 I + alpha (1 - alpha) e e^T   (a sum of PSD terms)
 //     l = 1/2 log det Sigma_y + 1/2 d^T Sigma_y^-1 d,  d = y - mu_y   (C = 1: log sy + d^2 / sy);  l -= 0.1 alpha for a learnt alpha
 //   posterior mean: the pixel is untouched (x = y) or replaced (x follows the prior),
 //     Sigma_p = Sigma_x + 1e-6 I,  log f = log N(y; mu_x, Sigma_p),  w = sigmoid(log(1 - alpha) - log alpha + log f),  pme = mu_x + w (y - mu_x)
-// Derivation, conditioning and measurements: DESIGN.md section 3.12.  Grid, pixel chunking and partial[b][chunk][2] are k_head's, so
-// k_head_final, k_fill_sigma_grad and k_head_vjp_final (head.hip) serve these kernels unchanged.
-#include "head_common.h"
+// Derivation, conditioning and measurements: DESIGN.md section 3.12.  Grid, pixel chunking (head_range), keep rule (head_vjp_kept) and
+// partial[b][chunk][2] are k_head's, so k_head_final and k_fill_sigma_grad (head.hip) serve these kernels unchanged.  The symmetric 3x3
+// helpers are head_math.h's.
 
 // Every product and sum below is rounded on its own: whether the compiler fuses a multiply into an add depends on how many uses the
 // product has, and g_net_out must not depend on whether g_noisy is requested (GY), bit for bit.  The kernels are HBM-bound.
+// The pragma holds for the functions defined after it, head_math.h's included: it stays above the include.
 #pragma clang fp contract(off)
-
-struct Sym3 { float m00, m01, m02, m11, m12, m22; };
-// adjugate of a symmetric 3x3 matrix; returns its determinant
-static __device__ __forceinline__ float sym3_adj(const Sym3& s, Sym3& c) {
-    c.m00 = s.m11 * s.m22 - s.m12 * s.m12; c.m01 = s.m02 * s.m12 - s.m01 * s.m22; c.m02 = s.m01 * s.m12 - s.m02 * s.m11;
-    c.m11 = s.m00 * s.m22 - s.m02 * s.m02; c.m12 = s.m01 * s.m02 - s.m00 * s.m12; c.m22 = s.m00 * s.m11 - s.m01 * s.m01;
-    return s.m00 * c.m00 + s.m01 * c.m01 + s.m02 * c.m02;
-}
-static __device__ __forceinline__ void sym3_mv(const Sym3& m, const float* v, float k, float* o) {
-    o[0] = (m.m00 * v[0] + m.m01 * v[1] + m.m02 * v[2]) * k;
-    o[1] = (m.m01 * v[0] + m.m11 * v[1] + m.m12 * v[2]) * k;
-    o[2] = (m.m02 * v[0] + m.m12 * v[1] + m.m22 * v[2]) * k;
-}
+#include "head_math.h"
 
 // alpha as the head sees it and d alpha / d est_raw: known: clamp(noise_param, 1e-3, 0.999); const / var: the reference's softplus remap
 // (denoiser.py:272-275) with an upper clamp, whose gradient is zero where it is active
@@ -95,14 +84,7 @@ static __device__ __forceinline__ void impulse_px(const float* mu, const float* 
         o.g[0] = gmu;
         o.g[1] = 2.f * a * gx;
     } else {
-        // Sigma_x = U U^T, U = [[a0,a1,a2],[0,a3,a4],[0,0,a5]]   (denoiser.py:246-255)
-        Sym3 x;
-        x.m00 = A[0] * A[0] + A[1] * A[1] + A[2] * A[2];
-        x.m01 = A[1] * A[3] + A[2] * A[4];
-        x.m02 = A[2] * A[5];
-        x.m11 = A[3] * A[3] + A[4] * A[4];
-        x.m12 = A[4] * A[5];
-        x.m22 = A[5] * A[5];
+        const Sym3 x = sym3_uut(A);
         const float e[3] = {mu[0] - 0.5f, mu[1] - 0.5f, mu[2] - 0.5f};
         float gmu[3] = {0.f, 0.f, 0.f};
         Sym3 gx = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};           // dL/dSigma_x as a symmetric matrix (k_head's convention: dL/dU = 2 G U)
@@ -133,7 +115,7 @@ static __device__ __forceinline__ void impulse_px(const float* mu, const float* 
                     gmu[c] = -sc * om * q[c] + 2.f * k * Ge[c];
                     o.gy[c] = sc * q[c];
                 }
-                gx.m00 = om * G.m00; gx.m01 = om * G.m01; gx.m02 = om * G.m02; gx.m11 = om * G.m11; gx.m12 = om * G.m12; gx.m22 = om * G.m22;
+                gx = sym3_scale(G, om);
                 const float gdotx = G.m00 * x.m00 + G.m11 * x.m11 + G.m22 * x.m22 + 2.f * (G.m01 * x.m01 + G.m02 * x.m02 + G.m12 * x.m12);
                 const float tr = G.m00 + G.m11 + G.m22;
                 const float eGe = e[0] * Ge[0] + e[1] * Ge[1] + e[2] * Ge[2];
@@ -142,8 +124,8 @@ static __device__ __forceinline__ void impulse_px(const float* mu, const float* 
             }
         }
         if (do_post) {
-            Sym3 sp = x, cp;
-            sp.m00 += 1e-6f; sp.m11 += 1e-6f; sp.m22 += 1e-6f;
+            const Sym3 sp = sym3_add_diag(x, 1e-6f, 1e-6f, 1e-6f);
+            Sym3 cp;
             // exact arithmetic has det Sigma_p >= 1e-18 and a quadratic form >= 0; the fp32 adjugate of a rank-deficient Sigma_x may not
             const float detp = fmaxf(sym3_adj(sp, cp), 1e-18f);
             const float rdp = 1.f / detp;
@@ -172,13 +154,7 @@ static __device__ __forceinline__ void impulse_px(const float* mu, const float* 
             }
         }
         o.g[0] = gmu[0]; o.g[1] = gmu[1]; o.g[2] = gmu[2];
-        // dL/dU = 2 G U on the upper triangle
-        o.g[3] = 2.f * (gx.m00 * A[0]);
-        o.g[4] = 2.f * (gx.m00 * A[1] + gx.m01 * A[3]);
-        o.g[5] = 2.f * (gx.m00 * A[2] + gx.m01 * A[4] + gx.m02 * A[5]);
-        o.g[6] = 2.f * (gx.m01 * A[1] + gx.m11 * A[3]);
-        o.g[7] = 2.f * (gx.m01 * A[2] + gx.m11 * A[4] + gx.m12 * A[5]);
-        o.g[8] = 2.f * (gx.m02 * A[2] + gx.m12 * A[4] + gx.m22 * A[5]);
+        sym3_dldu(gx, A, o.g + 3);
     }
 }
 
@@ -191,12 +167,10 @@ __global__ __launch_bounds__(HB) void k_head_impulse(ssdn_head_args a) {
     const float inv_total = 1.f / ((float)a.B * (float)HW);  // mean over pixels, then mean over the batch
     const ImpulseAlpha al = impulse_alpha(a.mode, a.noise_param, a.est_raw, b);
     float loss_acc = 0.f, gal_acc = 0.f, gabs = 0.f;
-    const long long per = (HW + a.nchunks - 1) / a.nchunks;
-    const long long p0 = (long long)blockIdx.x * per;
-    const long long p1 = p0 + per < HW ? p0 + per : HW;
+    const HeadRange r = head_range(HW, a.nchunks);
     const float* no = a.net_out + (long long)b * Cout * HW;
     const float* ny = a.noisy + (long long)b * C * HW;
-    for (long long p = p0 + threadIdx.x; p < p1; p += HB) {
+    for (long long p = r.p0 + threadIdx.x; p < r.p1; p += HB) {
         float mu[C], A[NA], y[C];
 #pragma unroll
         for (int c = 0; c < C; ++c) { mu[c] = no[c * HW + p]; y[c] = ny[c * HW + p]; }
@@ -241,20 +215,18 @@ __global__ __launch_bounds__(HB) void k_head_vjp_impulse(ssdn_head_vjp_args a) {
     const int b = blockIdx.y;
     const long long HW = (long long)a.H * a.W;
     const float wb = a.w ? a.w[b] : 0.f;
-    const bool skip = a.keep && !a.g_pme && !a.g_mu && a.w && wb == 1.f / (float)a.B;
+    const bool skip = head_vjp_kept(a.keep, a.g_pme, a.g_mu, a.w, wb, a.B);
     if (skip && !GY) return;                         // (block-uniform: before any barrier)
     const float sc = wb / (float)HW;        // LOSS[b] is the mean over the pixels of sample b
     const ImpulseAlpha al = impulse_alpha(a.mode, a.noise_param, a.est_raw, b);
     float gal_acc = 0.f, gabs = 0.f;
-    const long long per = (HW + a.nchunks - 1) / a.nchunks;
-    const long long p0 = (long long)blockIdx.x * per;
-    const long long p1 = p0 + per < HW ? p0 + per : HW;
+    const HeadRange r = head_range(HW, a.nchunks);
     const float* no = a.net_out + (long long)b * Cout * HW;
     const float* ny = a.noisy + (long long)b * C * HW;
     const float* gpp = a.g_pme ? a.g_pme + (long long)b * C * HW : nullptr;
     const float* gm = a.g_mu ? a.g_mu + (long long)b * C * HW : nullptr;
     float* go = a.g_net_out + (long long)b * Cout * HW;
-    for (long long p = p0 + threadIdx.x; p < p1; p += HB) {
+    for (long long p = r.p0 + threadIdx.x; p < r.p1; p += HB) {
         float mu[C], A[NA], y[C], gp[C];
 #pragma unroll
         for (int c = 0; c < C; ++c) { mu[c] = no[c * HW + p]; y[c] = ny[c * HW + p]; gp[c] = gpp ? gpp[c * HW + p] : 0.f; }
@@ -283,14 +255,9 @@ __global__ __launch_bounds__(HB) void k_head_vjp_impulse(ssdn_head_vjp_args a) {
     if (a.gmax) atomic_max_abs_block(a.gmax, gabs, sh);
 }
 
-// launch_head / launch_head_vjp (head.hip) have validated shape and pointers
+// launch_head / launch_head_vjp (head.hip) have validated shape, style, mode and pointers
 int launch_head_impulse(const ssdn_head_args* a, hipStream_t s) {
     if (a->diag) return ssdn_set_error("head: style 2 (impulse) with diag = 1 (DIAGONAL_COVARIANCE) is not supported");
-    if (a->mode < 0 || a->mode > 2) return ssdn_set_error("head: bad mode");
-    if (!a->net_out || !a->noisy || !a->partial) return ssdn_set_error("head: net_out, noisy and partial must be given");
-    if (a->want_grad && !a->g_net_out) return ssdn_set_error("head: want_grad needs g_net_out");
-    if (a->mode == 0 && !a->noise_param) return ssdn_set_error("head: mode known needs noise_param");
-    if (a->mode != 0 && !a->est_raw) return ssdn_set_error("head: modes const / var need est_raw");
     const dim3 grid(a->nchunks, a->B);
     if (a->C == 1) hipLaunchKernelGGL(k_head_impulse<1>, grid, dim3(HB), 0, s, *a);
     else hipLaunchKernelGGL(k_head_impulse<3>, grid, dim3(HB), 0, s, *a);

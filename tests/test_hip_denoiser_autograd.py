@@ -8,41 +8,9 @@ import torch
 import restate as R
 from test_head_vjp_cpu import VARIANTS, NPAR, head_inputs, upstream, head_vjp64, oracle_vjp, mse_vjp64
 from test_hip_denoiser import make_denoiser
+from head_ops import DEV, P, head_vjp_op, run_one          # (DEV, P and run_one: the other GPU test modules import them from here)
 
 pytestmark = pytest.mark.gpu
-
-DEV = torch.device("cuda:0")
-
-
-def P(t):
-    return t.data_ptr() if t is not None else None
-
-
-def run_one(ty, args):
-    from ssdn.hip.engine import OpList, current_stream
-    OpList([(ty, args)]).run(current_stream())
-    torch.cuda.synchronize()
-
-
-def head_vjp_op(net_out, noisy, npar, style, mode, est_raw, w, gp, gm, nchunks=2):
-    """one SSDN_OP_HEAD_VJP launch (keep = 0) on device copies -> (g_net_out, g_est, g_sigma_out)"""
-    from ssdn.hip import lib as L
-    from ssdn.hip.engine import STYLE, MODE
-    d = lambda t: None if t is None else t.to(DEV, torch.float32).contiguous()   # noqa: E731
-    B, ncomp, H, W = net_out.shape
-    C = noisy.shape[1]
-    f = dict(dtype=torch.float32, device=DEV)
-    no, y, npd, er, wd, gpd, gmd = d(net_out), d(noisy), d(npar), d(est_raw), d(w), d(gp), d(gm)
-    gno = torch.full((B, ncomp, H, W), float("nan"), **f)
-    partial = torch.zeros(B, nchunks, 2, **f)
-    g_est = torch.zeros(B, **f) if mode != "known" else None
-    g_sig = torch.zeros(B, 1, H, W, **f) if mode == "var" else None
-    gmax = torch.zeros(4, dtype=torch.int32, device=DEV)
-    gmax2 = torch.zeros(4, dtype=torch.int32, device=DEV)
-    a = L.HeadVjpArgs(P(no), P(y), P(npd), P(er), B, C, H, W, STYLE["poisson" if style.startswith("poisson") else "gauss"], MODE[mode],
-                      P(wd), P(gpd), P(gmd), 0, nchunks, P(gno), P(partial), P(gmax), P(g_est), P(g_sig), P(gmax2))
-    run_one("head_vjp", a)
-    return gno, g_est, g_sig, gmax
 
 
 def _cmp(a, b, rtol, atol_rel, what=""):
@@ -65,7 +33,8 @@ def test_head_vjp_op_vs_float64_autograd(ch, style, mode):
     B, H = net_out.shape[0], net_out.shape[2]
     w, gp, gm = upstream(B, ch, H, seed=11 + ch)
     est_raw = raw.mean(dim=(1, 2, 3)) if mode == "var" else raw
-    gno, g_est, g_sig, gmax = head_vjp_op(net_out, noisy, npar, style, mode, est_raw, w, gp, gm)
+    r = head_vjp_op(net_out, noisy, npar, style, mode, est_raw, w, gp, gm, g_noisy=False)
+    gno, g_est, g_sig, gmax = r["g_net_out"], r["g_est"], r["g_sig"], r["gmax"]
     og, oraw = oracle_vjp(net_out, noisy, npar, style, mode, raw, w, gp, gm)
     _cmp(gno, og, 2e-4, 1e-6 if ch == 1 else ATOL_C3, "op vs fp64 autograd %d/%s/%s:" % (ch, style, mode))
     assert float(np.int32(gmax[0].item()).view(np.float32)) == pytest.approx(float(gno.abs().max()), rel=1e-6)

@@ -9,31 +9,9 @@ import restate as R
 from test_head_vjp_cpu import VARIANTS, NPAR, head_inputs, upstream
 from test_denoiser_input_grad_cpu import head_dy64, oracle_dy
 from test_hip_denoiser_autograd import BIT_CASES, DEV, P, batch, run_one, seeded_denoiser, _cos_rel
+from head_ops import head_vjp_op
 
 pytestmark = pytest.mark.gpu
-
-
-def head_vjp_gy(net_out, noisy, npar, style, mode, est_raw, w, gp, gm, g_noisy=True, keep=0, nchunks=2, g_init=None, partial_init=None):
-    """one SSDN_OP_HEAD_VJP launch on device copies -> dict of g_net_out, partial, g_est, g_sigma_out, g_noisy (None when not requested)"""
-    from ssdn.hip import lib as L
-    from ssdn.hip.engine import STYLE, MODE
-    d = lambda t: None if t is None else t.to(DEV, torch.float32).contiguous()   # noqa: E731
-    B, ncomp, H, W = net_out.shape
-    C = noisy.shape[1]
-    f = dict(dtype=torch.float32, device=DEV)
-    no, y, npd, er, wd, gpd, gmd = d(net_out), d(noisy), d(npar), d(est_raw), d(w), d(gp), d(gm)
-    gno = torch.full((B, ncomp, H, W), float("nan"), **f) if g_init is None else g_init.to(DEV).clone()
-    partial = torch.zeros(B, nchunks, 2, **f) if partial_init is None else partial_init.to(DEV).clone()
-    g_est = torch.zeros(B, **f) if mode != "known" else None
-    g_sig = torch.zeros(B, 1, H, W, **f) if mode == "var" else None
-    gmax = torch.zeros(4, dtype=torch.int32, device=DEV)
-    gmax2 = torch.zeros(4, dtype=torch.int32, device=DEV)
-    gy = torch.full((B, C, H, W), float("nan"), **f) if g_noisy else None
-    a = L.HeadVjpArgs(P(no), P(y), P(npd), P(er), B, C, H, W, STYLE["poisson" if style.startswith("poisson") else "gauss"], MODE[mode],
-                      P(wd), P(gpd), P(gmd), keep, nchunks, P(gno), P(partial), P(gmax), P(g_est), P(g_sig), P(gmax2))
-    a.g_noisy = P(gy)
-    run_one("head_vjp", a)
-    return dict(g_net_out=gno, partial=partial, g_est=g_est, g_sig=g_sig, gmax=gmax, g_noisy=gy)
 
 
 # ---- a. teacher-forced head term ------------------------------------------------------------------------------------------------------
@@ -49,7 +27,7 @@ def test_head_vjp_g_noisy_vs_float64(ch, style, mode):
     B, H = net_out.shape[0], net_out.shape[2]
     w, gp, gm = upstream(B, ch, H, seed=13 + ch)
     est_raw = raw.mean(dim=(1, 2, 3)) if mode == "var" else raw
-    r = head_vjp_gy(net_out, noisy, npar, style, mode, est_raw, w, gp, gm)
+    r = head_vjp_op(net_out, noisy, npar, style, mode, est_raw, w, gp, gm)
     want = oracle_dy(net_out, noisy, npar, style, mode, raw, w, gp, gm, kernel_pme=True)
     got = r["g_noisy"].cpu().double()
     err = float((got - want).abs().max() / want.abs().max())
@@ -58,7 +36,7 @@ def test_head_vjp_g_noisy_vs_float64(ch, style, mode):
     g64 = head_dy64(net_out, noisy, npar, style, mode, est_raw.double() if est_raw is not None else None, w, gp, gm)
     np.testing.assert_allclose(got.numpy(), g64.numpy(), rtol=2e-4, atol=(GY_ATOL_C1 if ch == 1 else GY_ATOL_C3) * float(g64.abs().max()))
     # the other outputs are those of the launch without g_noisy, bit for bit
-    r0 = head_vjp_gy(net_out, noisy, npar, style, mode, est_raw, w, gp, gm, g_noisy=False)
+    r0 = head_vjp_op(net_out, noisy, npar, style, mode, est_raw, w, gp, gm, g_noisy=False)
     for k in ("g_net_out", "partial", "g_est", "g_sig", "gmax"):
         if r0[k] is not None:
             assert torch.equal(r[k], r0[k]) or (k == "g_net_out" and torch.equal(r[k].nan_to_num(7.0), r0[k].nan_to_num(7.0))), k
@@ -73,8 +51,8 @@ def test_head_vjp_keep_path_writes_g_noisy_only(ch, style, mode):
     w[1] = 0.5                                              # sample 1 is not the forward's d mean(LOSS): it is recomputed
     g_init = torch.full((B, net_out.shape[1], H, H), 7.0)
     p_init = torch.full((B, 2, 2), 3.0)
-    r = head_vjp_gy(net_out, noisy, npar, style, mode, est_raw, w, None, None, keep=1, g_init=g_init, partial_init=p_init)
-    full = head_vjp_gy(net_out, noisy, npar, style, mode, est_raw, w, None, None, keep=0)
+    r = head_vjp_op(net_out, noisy, npar, style, mode, est_raw, w, None, None, keep=1, g_init=g_init, partial_init=p_init)
+    full = head_vjp_op(net_out, noisy, npar, style, mode, est_raw, w, None, None, keep=0)
     for b in (0, 2):                                        # kept samples: gradient and partials untouched, g_noisy written
         assert torch.equal(r["g_net_out"][b].cpu(), g_init[b]) and torch.equal(r["partial"][b].cpu(), p_init[b])
     assert torch.equal(r["g_net_out"][1], full["g_net_out"][1])

@@ -13,7 +13,8 @@ import torch
 import restate as R
 from test_diag_cov_cpu import CASES, NPAR, diag_cfg, diag_head64, diag_inputs, oracle_diag, scatter9
 from test_hip_denoiser import _cat_state, _flat_grad_of, _flat_of
-from test_hip_denoiser_autograd import DEV, P, _cos_rel, batch, run_one
+from test_hip_denoiser_autograd import DEV, P, _cos_rel, batch
+from head_ops import head_op, head_vjp_op
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,54 +37,6 @@ def diag_denoiser(style="gauss25", mode="known", ch=3, diag=True, seeded=True):
     return d
 
 
-def _dev(t):
-    return None if t is None else t.to(DEV, torch.float32).contiguous()
-
-
-def head_op(net_out, noisy, npar, style, mode, est_raw, nchunks=2):
-    """SSDN_OP_HEAD_SSDN (diag = 1) + SSDN_OP_HEAD_FINAL on device copies"""
-    from ssdn.hip import lib as L
-    from ssdn.hip.engine import STYLE, MODE
-    B, _, H, W = net_out.shape
-    f = dict(dtype=torch.float32, device=DEV)
-    no, y, npd, er = _dev(net_out), _dev(noisy), _dev(npar), _dev(est_raw)
-    mu, pme = torch.full((B, 3, H, W), float("nan"), **f), torch.full((B, 3, H, W), float("nan"), **f)
-    mstd = torch.full((B, H, W), float("nan"), **f)
-    nstd = torch.full((B, H, W) if style.startswith("poisson") else (B,), float("nan"), **f)
-    gno = torch.full((B, 6, H, W), float("nan"), **f)
-    partial = torch.zeros(B, nchunks, 2, **f)
-    gmax = torch.zeros(4, dtype=torch.int32, device=DEV)
-    sty = STYLE["poisson" if style.startswith("poisson") else "gauss"]
-    run_one("head_ssdn", L.HeadArgs(P(no), P(y), P(npd), P(er), B, 3, H, W, sty, MODE[mode], 1, P(mu), P(pme), P(mstd), P(nstd), P(gno),
-                                    P(partial), nchunks, P(gmax), 1))
-    loss, g_est = torch.zeros(B, **f), torch.zeros(B, **f)
-    g_sig, gmax2 = torch.zeros(B, 1, H, W, **f), torch.zeros(4, dtype=torch.int32, device=DEV)
-    run_one("head_final", L.HeadFinalArgs(P(partial), B, nchunks, H, W, MODE[mode], P(loss), P(g_est) if mode != "known" else None,
-                                          P(g_sig) if mode == "var" else None, P(gmax2) if mode == "var" else None))
-    return dict(loss=loss, mu=mu, pme=pme, model_std=mstd, noise_std=nstd, g_net_out=gno, partial=partial, g_est=g_est, g_sig=g_sig,
-                gmax=gmax)
-
-
-def vjp_op(net_out, noisy, npar, style, mode, est_raw, w, gp, gm, keep=0, nchunks=2, g_init=None, partial_init=None):
-    """SSDN_OP_HEAD_VJP (diag = 1, g_noisy requested) on device copies"""
-    from ssdn.hip import lib as L
-    from ssdn.hip.engine import STYLE, MODE
-    B, _, H, W = net_out.shape
-    f = dict(dtype=torch.float32, device=DEV)
-    gno = torch.full((B, 6, H, W), float("nan"), **f) if g_init is None else g_init.clone()
-    partial = torch.zeros(B, nchunks, 2, **f) if partial_init is None else partial_init.clone()
-    g_est = torch.zeros(B, **f) if mode != "known" else None
-    g_sig = torch.zeros(B, 1, H, W, **f) if mode == "var" else None
-    gmax, gmax2 = torch.zeros(4, dtype=torch.int32, device=DEV), torch.zeros(4, dtype=torch.int32, device=DEV)
-    gy = torch.full((B, 3, H, W), float("nan"), **f)
-    ins = [_dev(t) for t in (net_out, noisy, npar, est_raw, w, gp, gm)]
-    a = L.HeadVjpArgs(*[P(t) for t in ins[:4]], B, 3, H, W, STYLE["poisson" if style.startswith("poisson") else "gauss"], MODE[mode],
-                      *[P(t) for t in ins[4:]], keep, nchunks, P(gno), P(partial), P(gmax), P(g_est), P(g_sig), P(gmax2))
-    a.g_noisy, a.diag = P(gy), 1
-    run_one("head_vjp", a)
-    return dict(g_net_out=gno, partial=partial, g_est=g_est, g_sig=g_sig, g_noisy=gy)
-
-
 def close(a, b, rtol, atol, what=""):
     b = b.detach().cpu().double().numpy() if isinstance(b, torch.Tensor) else np.asarray(b)
     np.testing.assert_allclose(a.detach().cpu().double().numpy().reshape(b.shape), b, rtol=rtol, atol=atol, err_msg=what)
@@ -95,7 +48,7 @@ def test_diag_head_op_vs_float64(style, mode):
     net_out, noisy, npar, raw = diag_inputs(style, mode)
     B, H = net_out.shape[0], net_out.shape[2]
     est_raw = raw.mean(dim=(1, 2, 3)) if mode == "var" else raw
-    r = head_op(net_out, noisy, npar, style, mode, est_raw)
+    r = head_op(net_out, noisy, npar, style, mode, est_raw, diag=1)
     o, g, graw, _ = oracle_diag(net_out, noisy, npar, style, mode, raw, w=torch.full((B,), 1.0 / B))
     close(r["loss"], o["loss"].view(B), 2e-5, 1e-6, "loss")
     close(r["mu"], net_out[:, :3], 0, 0, "mu")
@@ -122,7 +75,7 @@ def test_diag_head_vjp_op_vs_float64(style, mode):
     g = torch.Generator().manual_seed(17)
     w, gp, gm = torch.randn(B, generator=g), torch.randn(B, 3, H, H, generator=g), torch.randn(B, 3, H, H, generator=g)
     for terms in ((w, gp, gm), (w, None, None), (None, gp, None), (None, None, gm)):
-        r = vjp_op(net_out, noisy, npar, style, mode, est_raw, *terms)
+        r = head_vjp_op(net_out, noisy, npar, style, mode, est_raw, *terms, diag=1)
         _, og, oraw, ody = oracle_diag(net_out, noisy, npar, style, mode, raw, *terms)
         close(r["g_net_out"], og, 2e-4, 2e-6 * float(og.abs().max()), "g_net_out")
         close(r["g_noisy"], ody, 2e-4, 4.1e-6 * float(ody.abs().max()) + 1e-30, "g_noisy")
@@ -131,14 +84,14 @@ def test_diag_head_vjp_op_vs_float64(style, mode):
         if mode == "var":
             close(r["g_sig"], oraw, 2e-4, 1e-6 * float(oraw.abs().max()) + 1e-12, "g_sigma_out")
     # keep: a sample asking for exactly d mean(LOSS) keeps the forward's g_net_out and partials, bit for bit, and still writes g_noisy
-    f = head_op(net_out, noisy, npar, style, mode, est_raw)
-    r = vjp_op(net_out, noisy, npar, style, mode, est_raw, torch.full((B,), 1.0 / B), None, None, keep=1, g_init=f["g_net_out"],
-               partial_init=f["partial"])
+    f = head_op(net_out, noisy, npar, style, mode, est_raw, diag=1)
+    r = head_vjp_op(net_out, noisy, npar, style, mode, est_raw, torch.full((B,), 1.0 / B), None, None, diag=1, keep=1, g_init=f["g_net_out"],
+                    partial_init=f["partial"])
     assert torch.equal(r["g_net_out"], f["g_net_out"]) and torch.equal(r["partial"], f["partial"])
     _, _, _, ody = oracle_diag(net_out, noisy, npar, style, mode, raw, torch.full((B,), 1.0 / B))
     close(r["g_noisy"], ody, 2e-4, 4.1e-6 * float(ody.abs().max()), "g_noisy (keep)")
     # without keep the same request recomputes what the forward wrote
-    r = vjp_op(net_out, noisy, npar, style, mode, est_raw, torch.full((B,), 1.0 / B), None, None)
+    r = head_vjp_op(net_out, noisy, npar, style, mode, est_raw, torch.full((B,), 1.0 / B), None, None, diag=1)
     close(r["g_net_out"], f["g_net_out"], 1e-5, 1e-6 * float(f["g_net_out"].abs().max()), "VJP of mean(LOSS) vs the forward's gradient")
 
 

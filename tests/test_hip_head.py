@@ -8,22 +8,16 @@ import pytest
 import torch
 
 import restate as R
+from head_ops import P, head_op, head_vjp_op, run_one
+from test_diag_cov_cpu import diag_inputs
+from test_head_vjp_cpu import head_inputs, upstream
+from test_impulse_cpu import impulse_inputs
 
 pytestmark = pytest.mark.gpu
 
 
 def dev():
     return torch.device("cuda:0")
-
-
-def run_one(ty, args):
-    from ssdn.hip.engine import OpList, current_stream
-    OpList([(ty, args)]).run(current_stream())
-    torch.cuda.synchronize()
-
-
-def P(t):
-    return t.data_ptr() if t is not None else None
 
 
 @pytest.mark.parametrize("style,npar", [("gauss25", 25 / 255.0), ("poisson30", 30.0)])
@@ -37,7 +31,6 @@ def test_ssdn_head_vs_reference(golden_dir, style, npar, mode, ch):
     up to 4.6e-4 from the exact value on these inputs (measured), while the kernel's algebraically equal
     mu + Sx (Sx+Sn)^-1 (y-mu) form stays within 2e-6 of it."""
     from ssdn.hip import lib as L
-    from ssdn.hip.engine import STYLE, MODE
     g = np.load(os.path.join(golden_dir, "g_head_%s_%s_c%d.npz" % (style, mode, ch)))
     B, H = 2, 8
     ncomp = ch + ch * (ch + 1) // 2
@@ -45,7 +38,6 @@ def test_ssdn_head_vs_reference(golden_dir, style, npar, mode, ch):
     net_out[:, :ch] = R.hash_tensor((B, ch, H, H), 42, 0.05, 0.95)
     noisy = R.hash_tensor((B, ch, H, H), 43, 0.0, 1.0)
     f = dict(dtype=torch.float32, device=dev())
-    d_no, d_y = net_out.to(dev()), noisy.to(dev())
     d_np = torch.full((B,), npar, **f)
     est_raw = None
     if mode == "var":
@@ -55,22 +47,9 @@ def test_ssdn_head_vs_reference(golden_dir, style, npar, mode, ch):
         np.testing.assert_allclose(est_raw.cpu().numpy(), raw_map.mean(dim=(1, 2, 3)).cpu().numpy(), rtol=1e-6)
     if mode == "const":
         est_raw = torch.full((1,), 1.7, **f)
-    nchunks = 2
-    mu, pme = torch.zeros(B, ch, H, H, **f), torch.zeros(B, ch, H, H, **f)
-    mstd = torch.zeros(B, H, H, **f)
-    nstd = torch.zeros((B, H, H) if style.startswith("poisson") else (B,), **f)
-    gno = torch.full((B, ncomp, H, H), float("nan"), **f)
-    partial = torch.zeros(B, nchunks, 2, **f)
-    gmax = torch.zeros(4, dtype=torch.int32, device=dev())
-    sty = STYLE["poisson" if style.startswith("poisson") else "gauss"]
-    run_one("head_ssdn", L.HeadArgs(P(d_no), P(d_y), P(d_np), P(est_raw), B, ch, H, H, sty, MODE[mode], 1, P(mu), P(pme), P(mstd), P(nstd),
-                                    P(gno), P(partial), nchunks, P(gmax)))
-    loss = torch.zeros(B, **f)
-    g_est = torch.zeros(B, **f)
-    g_sig = torch.zeros(B, 1, H, H, **f)
-    gmax2 = torch.zeros(4, dtype=torch.int32, device=dev())
-    run_one("head_final", L.HeadFinalArgs(P(partial), B, nchunks, H, H, MODE[mode], P(loss), P(g_est) if mode != "known" else None,
-                                          P(g_sig) if mode == "var" else None, P(gmax2) if mode == "var" else None))
+    r = head_op(net_out, noisy, d_np, style, mode, est_raw)
+    loss, mu, pme, mstd, nstd = r["loss"], r["mu"], r["pme"], r["model_std"], r["noise_std"]
+    gno, g_est, g_sig, gmax = r["g_net_out"], r["g_est"], r["g_sig"], r["gmax"]
 
     def close(a, b, rtol, atol):
         b = b.detach().numpy() if isinstance(b, torch.Tensor) else np.asarray(b)
@@ -114,6 +93,49 @@ def test_ssdn_head_vs_reference(golden_dir, style, npar, mode, ch):
         close(g_est[:1], g["g_raw"].reshape(1), 5e-4, 1e-8)
     if mode == "var":
         close(g_sig, g["g_raw"], 5e-4, 1e-9)
+
+
+# head kind, channels, style, mode
+CHUNK_CASES = [("full", 1, "gauss25", "known"), ("full", 1, "poisson30", "const"), ("full", 3, "gauss25", "known"),
+               ("full", 3, "poisson30", "const"), ("diag", 3, "gauss25", "var"), ("impulse", 1, "impulse", "known"),
+               ("impulse", 3, "impulse", "known")]
+
+
+@pytest.mark.parametrize("kind,ch,style,mode", CHUNK_CASES)
+def test_head_chunking_does_not_change_a_pixel(kind, ch, style, mode):
+    """529 pixels per sample in 1, 2 and 3 blocks of 256 threads: a block's pixel loop makes up to three trips and its last trip, and the
+    last block (265 / 264 and 177 / 177 / 175 pixels), are ragged.  What a kernel writes per pixel is the same bits however the pixels are
+    dealt out; loss, g_est and g_sigma_out are the same sums in another order (rtol 1e-5, as for the re-association in
+    tests/test_hip_diag_cov.py::test_diag_head_vjp_op_vs_float64)."""
+    B, H = 3, 23
+    if kind == "diag":
+        net_out, noisy, npar, raw = diag_inputs(style, mode, B=B, H=H)
+    elif kind == "impulse":
+        net_out, noisy, npar, raw = impulse_inputs(ch, mode, 0.5, B=B, H=H)
+    else:
+        net_out, noisy, npar, raw = head_inputs(ch, style, mode, B=B, H=H)
+    est_raw = raw.mean(dim=(1, 2, 3)) if mode == "var" else raw
+    w, gp, gm = upstream(B, ch, H, seed=29 + ch)
+    diag = int(kind == "diag")
+    fwd, vjp = {}, {}
+    for n in (1, 2, 3):
+        fwd[n] = head_op(net_out, noisy, npar, style, mode, est_raw, diag=diag, nchunks=n)
+        vjp[n] = head_vjp_op(net_out, noisy, npar, style, mode, est_raw, w, gp, gm, diag=diag, nchunks=n)
+    pixel_f, pixel_v = ("mu", "pme", "model_std", "noise_std", "g_net_out"), ("g_net_out", "g_noisy")
+    for k in pixel_f:
+        assert torch.isfinite(fwd[1][k]).all(), k
+    for k in pixel_v:
+        assert torch.isfinite(vjp[1][k]).all(), k
+    sums = [("loss", fwd)] + ([("g_est", fwd), ("g_est", vjp)] if mode != "known" else []) + ([("g_sig", fwd), ("g_sig", vjp)] if mode == "var" else [])
+    for n in (2, 3):
+        for k in pixel_f:
+            assert torch.equal(fwd[n][k], fwd[1][k]), "forward %s, nchunks %d: %d elements differ" % (k, n, int((fwd[n][k] != fwd[1][k]).sum()))
+        for k in pixel_v:
+            assert torch.equal(vjp[n][k], vjp[1][k]), "vjp %s, nchunks %d: %d elements differ" % (k, n, int((vjp[n][k] != vjp[1][k]).sum()))
+        for k, runs in sums:
+            a, b = runs[n][k].cpu().double().numpy(), runs[1][k].cpu().double().numpy()
+            print("%s %s nchunks %d vs 1: max rel diff %.3e" % ("forward" if runs is fwd else "vjp", k, n, float(np.max(np.abs(a - b) / np.maximum(np.abs(b), 1e-300)))))
+            np.testing.assert_allclose(a, b, rtol=1e-5, atol=0)
 
 
 def test_mse_and_masked_mse_vs_reference(golden_dir):

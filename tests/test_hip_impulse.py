@@ -19,16 +19,13 @@ import torch
 import restate as R
 from test_impulse_cpu import impulse_cfg, impulse_forward_paper, impulse_head, impulse_inputs
 from test_hip_denoiser import _cat_state, _flat_grad_of, _flat_of
-from test_hip_denoiser_autograd import DEV, P, _cos_rel, run_one
+from test_hip_denoiser_autograd import DEV, P, _cos_rel
+from head_ops import head_op, head_vjp_op
 from test_hip_noise import _run as noise_run
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STYLE_IMPULSE = 2
-
-
-def _dev(t):
-    return None if t is None else t.to(DEV, torch.float32).contiguous()
 
 
 def close(a, b, rtol, atol, what=""):
@@ -164,49 +161,6 @@ def test_noise_op_other_styles_are_the_parents_bit_for_bit(style):
 HEAD_CASES = [(C, mode, alpha) for C in (1, 3) for mode in ("known", "const", "var") for alpha in (0.05, 0.5)] + [(3, "const", 0.0965)]
 
 
-def head_op(net_out, noisy, npar, mode, est_raw, nchunks=2, diag=0):
-    """SSDN_OP_HEAD_SSDN (style 2) + SSDN_OP_HEAD_FINAL on device copies; every output NaN-poisoned first"""
-    from ssdn.hip import lib as L
-    from ssdn.hip.engine import MODE
-    B, Cout, H, W = net_out.shape
-    C = noisy.shape[1]
-    f = dict(dtype=torch.float32, device=DEV)
-    nan = lambda *s: torch.full(s, float("nan"), **f)    # noqa: E731
-    no, y, npd, er = _dev(net_out), _dev(noisy), _dev(npar), _dev(est_raw)
-    mu, pme, mstd, nstd, gno = nan(B, C, H, W), nan(B, C, H, W), nan(B, H, W), nan(B), nan(B, Cout, H, W)
-    partial = nan(B, nchunks, 2)
-    gmax = torch.zeros(4, dtype=torch.int32, device=DEV)
-    run_one("head_ssdn", L.HeadArgs(P(no), P(y), P(npd), P(er), B, C, H, W, STYLE_IMPULSE, MODE[mode], 1, P(mu), P(pme), P(mstd), P(nstd), P(gno),
-                                    P(partial), nchunks, P(gmax), diag))
-    loss, g_est = nan(B), torch.zeros(B, **f)
-    g_sig, gmax2 = nan(B, 1, H, W), torch.zeros(4, dtype=torch.int32, device=DEV)
-    run_one("head_final", L.HeadFinalArgs(P(partial), B, nchunks, H, W, MODE[mode], P(loss), P(g_est) if mode != "known" else None,
-                                          P(g_sig) if mode == "var" else None, P(gmax2) if mode == "var" else None))
-    return dict(loss=loss, mu=mu, pme=pme, model_std=mstd, noise_std=nstd, g_net_out=gno, partial=partial, g_est=g_est, g_sig=g_sig,
-                gmax=gmax)
-
-
-def vjp_op(net_out, noisy, npar, mode, est_raw, w, gp, gm, keep=0, nchunks=2, g_init=None, partial_init=None, want_gy=True):
-    """SSDN_OP_HEAD_VJP (style 2) on device copies"""
-    from ssdn.hip import lib as L
-    from ssdn.hip.engine import MODE
-    B, Cout, H, W = net_out.shape
-    C = noisy.shape[1]
-    f = dict(dtype=torch.float32, device=DEV)
-    gno = torch.full((B, Cout, H, W), float("nan"), **f) if g_init is None else g_init.clone()
-    partial = torch.zeros(B, nchunks, 2, **f) if partial_init is None else partial_init.clone()
-    g_est = torch.zeros(B, **f) if mode != "known" else None
-    g_sig = torch.full((B, 1, H, W), float("nan"), **f) if mode == "var" else None
-    gmax, gmax2 = torch.zeros(4, dtype=torch.int32, device=DEV), torch.zeros(4, dtype=torch.int32, device=DEV)
-    gy = torch.full((B, C, H, W), float("nan"), **f) if want_gy else None
-    ins = [_dev(t) for t in (net_out, noisy, npar, est_raw, w, gp, gm)]
-    a = L.HeadVjpArgs(*[P(t) for t in ins[:4]], B, C, H, W, STYLE_IMPULSE, MODE[mode], *[P(t) for t in ins[4:]], keep, nchunks, P(gno),
-                      P(partial), P(gmax), P(g_est), P(g_sig), P(gmax2))
-    a.g_noisy, a.diag = P(gy), 0
-    run_one("head_vjp", a)
-    return dict(g_net_out=gno, partial=partial, g_est=g_est, g_sig=g_sig, g_noisy=gy, gmax=gmax)
-
-
 def _est(raw, mode):
     return raw.mean(dim=(1, 2, 3)) if mode == "var" else raw
 
@@ -237,7 +191,7 @@ def test_impulse_head_op_vs_float64(C, mode, alpha):
     wm = torch.full((B,), 1.0 / B)
     m = impulse_head(net_out, noisy, npar, mode, est_raw, w=wm)
     fig = _fp32_yardstick(net_out, noisy, npar, mode, est_raw, m, w=wm)
-    r = head_op(net_out, noisy, npar, mode, est_raw)
+    r = head_op(net_out, noisy, npar, "impulse", mode, est_raw)
     close(r["loss"], m["loss"], 2e-5, 1e-6, "loss")
     close(r["mu"], net_out[:, :C], 0, 0, "mu")
     close(r["pme"], m["pme"], 2e-5, _atol(5e-6, fig["pme"]), "pme")
@@ -252,7 +206,7 @@ def test_impulse_head_op_vs_float64(C, mode, alpha):
         close(r["g_sig"], want, 2e-4, _atol(1e-10, fig["g_est"] / (H * H)), "g_sigma_out")
     assert float(np.int32(r["gmax"][0].item()).view(np.float32)) == pytest.approx(float(r["g_net_out"].abs().max()), rel=1e-6)      # the sentinel: max |g| as written
     # another chunking: the per-pixel outputs do not change
-    r2 = head_op(net_out, noisy, npar, mode, est_raw, nchunks=1)
+    r2 = head_op(net_out, noisy, npar, "impulse", mode, est_raw, nchunks=1)
     assert torch.equal(r2["pme"], r["pme"]) and torch.equal(r2["g_net_out"], r["g_net_out"])
 
 
@@ -266,7 +220,7 @@ def test_impulse_head_vjp_op_vs_float64(C, mode, alpha):
     for terms in ((w, gp, gm), (w, None, None), (None, gp, None), (None, None, gm)):
         m = impulse_head(net_out, noisy, npar, mode, est_raw, *terms)
         fig = _fp32_yardstick(net_out, noisy, npar, mode, est_raw, m, *terms)
-        r = vjp_op(net_out, noisy, npar, mode, est_raw, *terms)
+        r = head_vjp_op(net_out, noisy, npar, "impulse", mode, est_raw, *terms)
         og, ody = m["g_net_out"], m["g_noisy"]
         close(r["g_net_out"], og, 2e-4, _atol(2e-6 * float(og.abs().max()), fig["g_net_out"]), "g_net_out")
         close(r["g_noisy"], ody, 2e-4, _atol(4.1e-6 * float(ody.abs().max()) + 1e-30, fig["g_noisy"]), "g_noisy")
@@ -277,19 +231,19 @@ def test_impulse_head_vjp_op_vs_float64(C, mode, alpha):
             close(r["g_sig"], want, 2e-4, _atol(1e-6 * float(want.abs().max()) + 1e-12, fig["g_est"] / (H * H)), "g_sigma_out")
         assert float(np.int32(r["gmax"][0].item()).view(np.float32)) == pytest.approx(float(r["g_net_out"].abs().max()), rel=1e-6)
         # g_noisy = NULL: every other output unchanged, bit for bit
-        r0 = vjp_op(net_out, noisy, npar, mode, est_raw, *terms, want_gy=False)
+        r0 = head_vjp_op(net_out, noisy, npar, "impulse", mode, est_raw, *terms, g_noisy=False)
         assert torch.equal(r0["g_net_out"], r["g_net_out"]) and torch.equal(r0["partial"], r["partial"])
     # keep: a sample asking for exactly d mean(LOSS) keeps the forward's g_net_out and partials, bit for bit, and still writes g_noisy
     wm = torch.full((B,), 1.0 / B)
-    f = head_op(net_out, noisy, npar, mode, est_raw)
-    r = vjp_op(net_out, noisy, npar, mode, est_raw, wm, None, None, keep=1, g_init=f["g_net_out"], partial_init=f["partial"])
+    f = head_op(net_out, noisy, npar, "impulse", mode, est_raw)
+    r = head_vjp_op(net_out, noisy, npar, "impulse", mode, est_raw, wm, None, None, keep=1, g_init=f["g_net_out"], partial_init=f["partial"])
     assert torch.equal(r["g_net_out"], f["g_net_out"]) and torch.equal(r["partial"], f["partial"])
     mk = impulse_head(net_out, noisy, npar, mode, est_raw, wm)
     ody = mk["g_noisy"]
     close(r["g_noisy"], ody, 2e-4, _atol(4.1e-6 * float(ody.abs().max()), _fp32_yardstick(net_out, noisy, npar, mode, est_raw, mk, wm)["g_noisy"]),
           "g_noisy (keep)")
     # without keep the same request recomputes what the forward wrote
-    r = vjp_op(net_out, noisy, npar, mode, est_raw, wm, None, None)
+    r = head_vjp_op(net_out, noisy, npar, "impulse", mode, est_raw, wm, None, None)
     close(r["g_net_out"], f["g_net_out"], 1e-5, 1e-6 * float(f["g_net_out"].abs().max()), "VJP of mean(LOSS) vs the forward's gradient")
 
 
