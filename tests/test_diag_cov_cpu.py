@@ -251,7 +251,7 @@ def test_forward_backward_lowering_six_outputs(dev_cus):
     from test_lowering_cpu import _check_lowering
     torch.set_default_dtype(torch.float64)
     try:
-        _check_lowering(3, 6, True, 2, 32, dev_cus)
+        _check_lowering(3, 6, True, 2, 32, 32, dev_cus)
     finally:
         torch.set_default_dtype(torch.float32)
 

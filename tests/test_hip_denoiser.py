@@ -297,6 +297,101 @@ def test_eval_forward_any_square_size():
     assert abs(float(R.psnr(o, clean) - R.psnr(r["out"], clean))) <= 0.05
 
 
+@pytest.mark.parametrize("transpose,shape", [(False, (50, 90)), (True, (90, 50))])
+def test_eval_forward_non_square_size(transpose, shape):
+    """Validation of a plain-network run (N2C here; ssdn/train.py pads such a validation set to multiples of 32 per side, not to squares: BSD
+    at 352x512 / 512x352, Kodak at 512x768 / 768x512, batch 1; here 64x96 and its transpose 96x64 to stay small, ragged tiles down to a 2x3
+    stage): IMG_DENOISED against the oracle, the device's per-sample PSNR over the un-padded extent (also non-square) against the host
+    formula on the device's own output, and the PSNR criterion of BASELINE.json against the oracle path.
+    Measured: relative L2 8.1e-4 (64x96) and 7.7e-4 (96x64), PSNR within 2e-3 dB of the oracle path, device PSNR equal to the host's to 1e-6."""
+    from ssdn.denoiser import Denoiser
+    from ssdn.datasets import NoisyDataset
+    from ssdn.params import PipelineOutput
+    MD = NoisyDataset.Metadata
+    d = make_denoiser("n2c", "gauss25", "known", 3)
+    p = R.make_params(3, 3, False, seed=5)
+    d.get_model(Denoiser.MODEL, False).load_state_dict(R.reference_state_dict(p))
+    d.mark_dirty()
+    d.eval()
+    x, clean = R.hash_tensor((1, 3, 64, 96), 77, 0, 1), R.hash_tensor((1, 3, 64, 96), 78, 0, 1)
+    if transpose:
+        x, clean = x.transpose(2, 3).contiguous(), clean.transpose(2, 3).contiguous()
+    e1, e2 = shape
+    data = [x, None, {MD.INPUT_NOISE_VALUES: torch.full((1, 1, 1, 1), 25 / 255.0), MD.CLEAN: clean, MD.IMAGE_SHAPE: torch.tensor([[3, e1, e2]])}]
+    with torch.no_grad():
+        out = d.run_pipeline(data)
+        per = d.accumulate_metrics(data, "valid", with_loss=False, per_sample=True)
+    o = out[PipelineOutput.IMG_DENOISED].cpu()
+    assert tuple(o.shape) == tuple(x.shape)
+    tr = R.CpuTrainer("n2c", 3, "gauss25", "known", params=p)
+    with torch.no_grad():
+        r = tr.forward(x, None, None)
+    rel = float((o - r["out"]).norm() / r["out"].norm())
+    want = float(-10 * torch.log10(((o[:, :, :e1, :e2].double() - clean[:, :, :e1, :e2].double()) ** 2).mean()))
+    dpsnr = abs(float(R.psnr(o, clean) - R.psnr(r["out"], clean)))
+    print("%s: rel %.3e, device PSNR %.6f host %.6f, PSNR difference to the oracle path %.2e dB" % (tuple(x.shape), rel, float(per["psnr_out"][0]), want, dpsnr))
+    assert rel <= 5e-3
+    np.testing.assert_allclose(per["psnr_out"].numpy(), [want], rtol=2e-5)
+    # PSNR criterion of BASELINE.json: same weights => within 0.05 dB of the reference path
+    assert dpsnr <= 0.05
+
+
+def _n2v_step_inputs(B, H, W):
+    """a Noise2Void minibatch at H != W: one masked pixel per 8x8 box, (row, col) as include/ssdn_hip.h documents ssdn_mse_args.coords --
+    half of the columns are >= H, so a swapped lookup leaves the plane"""
+    clean = R.hash_tensor((B, 3, H, W), 61, 0, 1)
+    noisy = torch.clamp(clean + R.hash_tensor((B, 3, H, W), 62, -1, 1) * 0.17, 0, 1)
+    ref = torch.clamp(clean + R.hash_tensor((B, 3, H, W), 63, -1, 1) * 0.17, 0, 1)
+    ii, jj = torch.meshgrid(torch.arange(H // 8), torch.arange(W // 8), indexing="ij")
+    inside = R.hash_tensor((B, (H // 8) * (W // 8), 2), 64, 0, 8).long().clamp(0, 7)
+    coords = torch.stack([ii.reshape(-1) * 8, jj.reshape(-1) * 8], 1)[None] + inside
+    return clean, noisy, ref, coords
+
+
+def test_n2v_training_step_non_square():
+    """One Noise2Void step at B = 2, 32x64 (BASELINE config 4's algorithm; k_conv_thin's smallest non-square image) next to the oracle
+    trainer from the same weights: the masked loss at test_training_trajectory's tolerance, every parameter tensor's gradient within the
+    bounds of tests/test_hip_ops.py::test_net_backward_end_to_end against the fp32 oracle (relative L2 <= 0.13, cosine >= 0.995).
+    Measured: loss within 2.4e-4 relative; worst parameter tensor relative L2 0.026, cosine 0.99968 (the fp16 CPU interpreter: 0.022, 0.99977)."""
+    from ssdn.denoiser import Denoiser
+    from ssdn.datasets import NoisyDataset
+    from ssdn.params import PipelineOutput
+    MD = NoisyDataset.Metadata
+    B, H, W = 2, 32, 64
+    clean, noisy, ref, coords = _n2v_step_inputs(B, H, W)
+    assert int(coords[0, :, 0].max()) < H and int((coords[0, :, 1] >= H).sum()) >= 8
+    p0 = R.make_params(3, 3, False, seed=5)
+    d = make_denoiser("n2v", "gauss25", "known", 3)
+    d.train()
+    tr = R.CpuTrainer("n2v", 3, "gauss25", "known", params={k: v.clone() for k, v in p0.items()})
+    net = d.get_model(Denoiser.MODEL, False)
+    nets = [(net, 0, tr.p)]
+    d.flat.copy_(_flat_of(d, nets, tr))
+    d.mark_dirty()
+    out = d.run_pipeline([noisy, ref, {MD.INPUT_NOISE_VALUES: torch.full((B, 1, 1, 1), 25 / 255.0), MD.CLEAN: clean, MD.MASK_COORDS: coords}])
+    d._last_engine.backward()
+    torch.cuda.synchronize()
+    r = tr.forward(noisy, ref, None, coords)
+    r["loss"].mean().backward()
+    loss = out[PipelineOutput.LOSS].detach().cpu().numpy()
+    print("loss %s oracle %s" % (loss.reshape(-1).tolist(), r["loss"].detach().reshape(-1).tolist()))
+    np.testing.assert_allclose(loss, r["loss"].detach().numpy(), rtol=1e-2, atol=2e-3)
+    o = out[PipelineOutput.IMG_DENOISED].detach().cpu()
+    assert float((o - r["out"].detach()).norm() / r["out"].detach().norm()) <= 5e-3
+    gd, gr = d.flat_grad.cpu(), _flat_grad_of(d, nets, tr)
+    bad, worst = [], [0.0, 1.0]
+    for l in net.layers:
+        for nm, sl in (("w", slice(l.w_off, l.w_off + l.M * l.cin * l.k * l.k)), ("b", slice(l.b_off, l.b_off + l.M))):
+            a, b = gd[sl], gr[sl]
+            cos = float((a * b).sum() / (a.norm() * b.norm() + 1e-30))
+            rel = float((a - b).norm() / (b.norm() + 1e-30))
+            worst = [max(worst[0], rel), min(worst[1], cos)]
+            if not (rel <= 0.13 and cos >= 0.995):
+                bad.append("%s.%s rel %.3e cos %.5f" % (l.name, nm, rel, cos))
+    print("worst parameter tensor vs fp32 oracle: rel %.4e cos %.6f" % tuple(worst))
+    assert not bad, bad
+
+
 def test_gradient_agreement_structured_images():
     """Parameter gradients at identical weights, device (fp16 activations, bf16 gradients) vs the fp32 oracle, on STRUCTURED images
     (smooth textures + gauss25 noise, reference-style He-normal init -- the regime the network trains in).  Measured with

@@ -157,6 +157,40 @@ def test_mse_and_masked_mse_vs_reference(golden_dir):
     np.testing.assert_allclose(grad.cpu().numpy(), g["g_out"], rtol=1e-5, atol=1e-9)
 
 
+# coordinates (row, col) as include/ssdn_hip.h documents them for ssdn_mse_args.coords: several rows (16x24: columns) are >= 16, so a lookup
+# that swaps the two lands on another pixel or off the plane (which the kernel skips); (20, 13) / (13, 20) twice: duplicates count twice
+@pytest.mark.parametrize("H,W,coords", [(16, 24, [(0, 0), (15, 23), (3, 17), (9, 20), (12, 16), (2, 5), (13, 20), (13, 20), (7, 23), (15, 1)]),
+                                        (24, 16, [(0, 0), (23, 15), (17, 3), (20, 9), (16, 12), (5, 2), (20, 13), (20, 13), (23, 7), (1, 15)])])
+def test_mse_and_masked_mse_on_a_non_square_plane(H, W, coords):
+    """SSDN_OP_MSE / SSDN_OP_MASK_MSE with H != W against float64 torch (oracle/restate.py's formulas: mean over C, H, W; masked: squared
+    errors summed over the coordinates, mean over C), gradient of mean_b(loss) compared in full from a NaN start"""
+    from ssdn.hip import lib as L
+    f = dict(dtype=torch.float32, device=dev())
+    B, Cn = 3, 3
+    out, tgt = R.hash_tensor((B, Cn, H, W), 51, 0, 1), R.hash_tensor((B, Cn, H, W), 52, 0, 1)
+    o64 = out.double().requires_grad_(True)
+    want = ((o64 - tgt.double()) ** 2).reshape(B, -1).mean(1)
+    want.mean().backward()
+    loss, grad = torch.zeros(B, **f), torch.full((B, Cn, H, W), float("nan"), **f)
+    gmax = torch.zeros(4, dtype=torch.int32, device=dev())
+    dout, dtgt = out.to(dev()), tgt.to(dev())
+    run_one("mse", L.MseArgs(P(dout), P(dtgt), None, 0, B, Cn, H, W, P(loss), P(grad), P(gmax)))
+    np.testing.assert_allclose(loss.cpu().numpy(), want.detach().numpy(), rtol=1e-5)
+    np.testing.assert_allclose(grad.cpu().numpy(), o64.grad.numpy(), rtol=1e-5, atol=1e-9)
+    assert float(np.int32(gmax[0].item()).view(np.float32)) == pytest.approx(float(o64.grad.abs().max()), rel=1e-5)
+    c = torch.tensor(coords, dtype=torch.int64)
+    o64 = out.double().requires_grad_(True)
+    diff = tgt.double()[:, :, c[:, 0], c[:, 1]] - o64[:, :, c[:, 0], c[:, 1]]
+    want = (diff ** 2).sum(-1).mean(1)
+    want.mean().backward()
+    dc = c.contiguous().to(dev())
+    loss, grad = torch.zeros(B, **f), torch.full((B, Cn, H, W), float("nan"), **f)
+    run_one("mask_mse", L.MseArgs(P(dout), P(dtgt), P(dc), len(coords), B, Cn, H, W, P(loss), P(grad), P(gmax)))
+    np.testing.assert_allclose(loss.cpu().numpy(), want.detach().numpy(), rtol=1e-5)
+    np.testing.assert_allclose(grad.cpu().numpy(), o64.grad.numpy(), rtol=1e-5, atol=1e-9)
+    assert int((grad != 0).sum()) == B * Cn * (len(set(coords)))
+
+
 def test_fused_adam_vs_oracle():
     from ssdn.hip import lib as L
     n = 100003
@@ -206,4 +240,41 @@ def test_metrics_kernel_vs_reference_psnr_and_host_formulas(golden_dir):
     np.testing.assert_allclose(per[:, 1].cpu().numpy(), want_p, rtol=2e-5)
     got = acc.cpu().numpy()
     assert got[1] == 0 and got[3] == 3 and got[5] == 0 and got[7] == 1 and got[9] == 0
+    np.testing.assert_allclose(got[6], float(nstd[0]) * 255, rtol=1e-6)
+
+
+@pytest.mark.parametrize("H,W,exts", [(16, 24, [(16, 24), (10, 20), (5, 24)]), (24, 16, [(24, 16), (20, 10), (24, 5)])])
+def test_metrics_kernel_on_a_non_square_plane(H, W, exts):
+    """SSDN_OP_METRICS with H != W: the whole plane and per-sample valid extents (e1 rows, e2 columns; one of them reaches past the
+    plane's other side, so swapped extents or a swapped row pitch crop other pixels) against the host PSNR formula in float64"""
+    from ssdn.hip import lib as L
+    a = R.hash_tensor((3, 3, H, W), 71, 0, 1)
+    b = torch.clamp(a + R.hash_tensor((3, 3, H, W), 72, -0.1, 0.1), 0, 1)
+    mu = torch.clamp(a + R.hash_tensor((3, 3, H, W), 73, -0.2, 0.2), 0, 1)
+    loss = R.hash_tensor((3,), 74, -1, 1)
+    mstd = R.hash_tensor((3, H, W), 75, 0, 0.1)
+    nstd = R.hash_tensor((3,), 76, 0.05, 0.2)
+    d = lambda t: t.to(dev()).contiguous()   # noqa: E731
+    da, db, dmu, dl, dm, dn = d(a), d(b), d(mu), d(loss), d(mstd), d(nstd)
+    per = torch.zeros(3, 8, device=dev())
+    acc = torch.zeros(16, device=dev())
+    args = L.MetricsArgs(P(db), P(dmu), P(da), P(dl), P(dm), P(dn), None, 3, 3, H, W, 3, P(per), P(acc))
+    run_one("metrics", args)
+    run_one("metrics", args)                       # accumulates
+    psnr = lambda x: (-10 * torch.log10(((x.double() - a.double()) ** 2).reshape(3, -1).mean(1)))   # noqa: E731
+    np.testing.assert_allclose(per[:, 1].cpu().numpy(), psnr(b).numpy(), rtol=2e-5)
+    want = [2 * float(loss.sum()), 2 * float(psnr(b).sum()), 2 * float(psnr(mu).sum()), 2 * float((nstd * 255).sum()),
+            2 * float((mstd * 255).reshape(3, -1).mean(1).sum())]
+    got = acc.cpu().numpy()
+    np.testing.assert_allclose(got[0:10:2], want, rtol=2e-5)
+    assert list(got[1:10:2]) == [6.0] * 5 and got[15] == 0
+    ext = torch.tensor(exts, dtype=torch.int32, device=dev())
+    acc.zero_()
+    args2 = L.MetricsArgs(P(db), None, P(da), None, None, P(dn), P(ext), 3, 3, H, W, 1, P(per), P(acc))
+    run_one("metrics", args2)
+    want_p = [float(-10 * torch.log10(((b[i, :, :e1, :e2].double() - a[i, :, :e1, :e2].double()) ** 2).mean())) for i, (e1, e2) in enumerate(exts)]
+    np.testing.assert_allclose(per[:, 1].cpu().numpy(), want_p, rtol=2e-5)
+    got = acc.cpu().numpy()
+    assert got[1] == 0 and got[3] == 3 and got[5] == 0 and got[7] == 1 and got[9] == 0
+    np.testing.assert_allclose(got[2], sum(want_p), rtol=2e-5)
     np.testing.assert_allclose(got[6], float(nstd[0]) * 255, rtol=1e-6)

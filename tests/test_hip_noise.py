@@ -127,37 +127,64 @@ def test_gaussian_shape_clipping_and_determinism():
 
 @pytest.mark.gpu
 def test_noise2void_manipulation_geometry(contract):
+    want = contract["n2v"]
+    assert want["coords_shape"] == [64, 2] and (want["coord_min"], want["coord_max"]) == (0, 63)    # what the reference gave at 64x64
+    _check_n2v_geometry(64, 64)
+
+
+# H != W: c0 is stratified over W and c1 over H, cell = (c0 / 8) * (H / 8) + c1 / 8, the copy window of an axis ends at that axis' size:
+# each of them lands outside the plane, on another box or on another window once H and W are swapped
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,W", [(32, 64), (64, 32)])
+def test_noise2void_manipulation_geometry_non_square(H, W):
+    _check_n2v_geometry(H, W)
+    # deterministic in (seed, offset), and a fresh offset picks other pixels
+    torch.manual_seed(1)
+    u8 = torch.randint(0, 256, (2, 3, H, W), dtype=torch.uint8)
+    a = _run(u8, 0, False, 0.1, 0.1, seed=3, offset=5, ref=True, n2v=True)
+    b = _run(u8, 0, False, 0.1, 0.1, seed=3, offset=5, ref=True, n2v=True)
+    assert all(torch.equal(a[k], b[k]) for k in ("noisy", "ref", "clean", "coords", "param"))
+    c = _run(u8, 0, False, 0.1, 0.1, seed=3, offset=6, ref=True, n2v=True)
+    assert not torch.equal(c["coords"], a["coords"]) and not torch.equal(c["noisy"], a["noisy"])
+    z = ((a["ref"] - a["clean"]) / 0.1).double().flatten()      # the second realisation: pure N(0, 1) over the whole non-square plane
+    # (mean of n = 12288 draws: 4 / sqrt(n) = 0.036; std dev: 4 / sqrt(2 n) = 0.026)
+    assert abs(float(z.mean())) < 0.036 and float(z.std()) == pytest.approx(1.0, abs=0.026)
+
+
+def _check_n2v_geometry(H, W):
     torch.manual_seed(0)
-    u8 = torch.randint(0, 256, (5, 3, 64, 64), dtype=torch.uint8)
+    nx, ny = W // 8, H // 8
+    u8 = torch.randint(0, 256, (5, 3, H, W), dtype=torch.uint8)
     plain = _run(u8, 0, True, 25 / 255.0, 25 / 255.0, seed=9, offset=2, ref=True)
     o = _run(u8, 0, True, 25 / 255.0, 25 / 255.0, seed=9, offset=2, ref=True, n2v=True)
-    want = contract["n2v"]
-    assert list(o["coords"].shape[1:]) == want["coords_shape"] and o["coords"].dtype == torch.int64
-    assert int(o["coords"].min()) >= want["coord_min"] and int(o["coords"].max()) <= want["coord_max"]
+    assert list(o["coords"].shape[1:]) == [nx * ny, 2] and o["coords"].dtype == torch.int64
+    assert int(o["coords"][..., 0].min()) >= 0 and int(o["coords"][..., 0].max()) <= W - 1
+    assert int(o["coords"][..., 1].min()) >= 0 and int(o["coords"][..., 1].max()) <= H - 1
     assert torch.equal(o["ref"], plain["ref"]) and torch.equal(o["clean"], plain["clean"])      # only the input is manipulated
     total_changed = 0
     for b in range(5):
         cs = o["coords"][b].tolist()
-        assert len({(x // 8, y // 8) for x, y in cs}) == 64                                  # one coordinate per 8 x 8 box
-        assert [(x // 8) * 8 + (y // 8) for x, y in cs] == list(range(64))                   # in the reference's box order
+        assert len({(x // 8, y // 8) for x, y in cs}) == nx * ny                             # one coordinate per 8 x 8 box
+        assert [(x // 8) * ny + (y // 8) for x, y in cs] == list(range(nx * ny))             # in the reference's box order
         diff = (o["noisy"][b] != plain["noisy"][b]).any(0)
         ys, xs = diff.nonzero(as_tuple=True)
         assert set(zip(xs.tolist(), ys.tolist())) <= {(x, y) for x, y in cs}                 # nothing else changed
         total_changed += int(diff.sum())
-        for x, y in cs:        # image[:, y, x] = image[:, ry, rx], (rx, ry) from [min(c - 2, 0), min(c + 2, 63)) without c, negatives wrap
-            cand_x = sorted({v % 64 for v in range(min(x - 2, 0), min(x + 2, 63)) if v != x})
-            cand_y = sorted({v % 64 for v in range(min(y - 2, 0), min(y + 2, 63)) if v != y})
+        for x, y in cs:        # image[:, y, x] = image[:, ry, rx], (rx, ry) from [min(c - 2, 0), min(c + 2, size - 1)) without c, negatives wrap
+            cand_x = sorted({v % W for v in range(min(x - 2, 0), min(x + 2, W - 1)) if v != x})
+            cand_y = sorted({v % H for v in range(min(y - 2, 0), min(y + 2, H - 1)) if v != y})
             src = (plain["noisy"][b][:, cand_y][:, :, cand_x] == o["noisy"][b][:, y, x].view(3, 1, 1)).all(0)
             assert bool(src.any()), (b, x, y)
-    assert total_changed >= 5 * 56                                                           # (a copied value may coincide with the old one)
+    assert total_changed >= 5 * (nx * ny - nx * ny // 8)                                     # (a copied value may coincide with the old one)
     # the interior window really is [0, c + 2): far-away sources occur
-    far = 0
+    far, cand = 0, 0
     for b in range(5):
         for x, y in o["coords"][b].tolist():
             if x >= 16 and y >= 16:
                 near = (plain["noisy"][b][:, max(y - 2, 0):y + 3, max(x - 2, 0):x + 3] == o["noisy"][b][:, y, x].view(3, 1, 1)).all(0)
                 far += int(not bool(near.any()))
-    assert far > 20
+                cand += 1
+    assert cand == 5 * (nx - 2) * (ny - 2) and far > cand // 9                                # (64x64: more than 20 of 180)
 
 
 @pytest.mark.gpu

@@ -16,7 +16,7 @@ import torch
 
 import restate as R
 from interp import Interp
-from test_lowering_cpu import flat_params
+from test_lowering_cpu import _hw_case, flat_params
 
 pytestmark = pytest.mark.gpu
 
@@ -138,29 +138,83 @@ CASES = [(3, 9, True, 2, 32, 0, 1), (1, 2, True, 1, 32, 0, 1), (3, 9, True, 4, 6
          (3, 9, True, 2, 32, 0, 2), (1, 2, True, 1, 32, 0, 2), (3, 3, False, 2, 64, 0, 2), (3, 9, True, 3, 64, 0, 2), (3, 1, False, 5, 32, 0, 2)]
 
 
+# H != W, plain network (cin, cout, False, B, H, W, cus, conv_mode) -> what the case must reach.  No square case can tell a kernel's H from
+# its W.  "first": the kernel of encode_block_1.0; "cdma": the stages (H, W) whose 3x3 layers k_cdma serves; both are read back from the
+# library's launch counters (ssdn_profile_read) per op and written, with each op's tiling and kc, to the case's teacher_forced_*.txt file under OUTDIR.
+HW_CASES = [
+    # conv_thin.hip::conv_thin_eligible needs H % 16 == 0 and W % 64 == 0: the smallest image k_conv_thin serves that is not square.  The
+    # 8x16 stage is the 128 pixels conv_chain.hip::chain_conv_ok excludes; 4x8, 2x4 and 1x2 are chain shapes.  conv_dma_eligible's size rule
+    # (N (H/16) (W/16) >= cus / 2) keeps k_cdma out: every 3x3 layer behind the first runs k_conv
+    ((3, 3, False, 2, 32, 64, 0, 1), dict(first="k_conv_thin", cdma=[])),
+    # the transpose: W % 64 != 0, so the first layer falls to k_conv; stages 16x8, 8x4, 4x2, 2x1
+    ((3, 3, False, 2, 64, 32, 0, 1), dict(first="k_conv", cdma=[])),
+    # the sigma network's shape: grid N (H/16) (W/64) of k_conv_thin has two tile columns; 8x32 is chain_conv_ok's 256-pixel rule, 4x16 its 64
+    ((3, 1, False, 1, 32, 128, 0, 1), dict(first="k_conv_thin", cdma=[])),
+    # mono, odd batch, the transpose of the above (32x8, 16x4)
+    ((1, 1, False, 3, 128, 32, 0, 1), dict(first="k_conv", cdma=[])),
+    # ragged tiles: stages 96, 48, 24, 12, 6, 3 wide (high): no power-of-two tile divides 3, and 3 is no chain shape
+    ((3, 3, False, 2, 64, 96, 0, 1), dict(first="k_conv", cdma=[])),
+    ((3, 3, False, 1, 96, 64, 0, 1), dict(first="k_conv_thin", cdma=[])),
+    # k_cdma forced (conv_dma_eligible(any_size)): every 3x3 layer of the stages with H % 16 == 0 and W % 16 == 0, strips of 2 x 4, 4 x 2
+    # and 6 x 4 tiles of 16x16 pixels (96x64: 24x16 has H % 16 != 0 and stays with k_conv)
+    ((3, 3, False, 2, 32, 64, 0, 2), dict(first="k_conv_thin", cdma=[(32, 64), (16, 32)])),
+    ((3, 3, False, 2, 64, 32, 0, 2), dict(first="k_cdma", cdma=[(64, 32), (32, 16)])),
+    ((3, 3, False, 1, 96, 64, 0, 2), dict(first="k_conv_thin", cdma=[(96, 64), (48, 32)])),
+    # 6 and 3 tile columns: the strip walk of k_cdma divides by tiles_x with a reciprocal multiply (CdAux.tx_magic), and no other case has a
+    # divisor that is not a power of two (the 352-wide validation images of a training run have 22 and 11)
+    ((3, 3, False, 2, 64, 96, 0, 2), dict(first="k_cdma", cdma=[(64, 96), (32, 48)])),
+    # k_cdma by conv_dma_eligible's default rule: 16 * 2 * 4 = 128 tiles = one per two CUs of images larger than one tile (H W > 256) at full
+    # resolution; the 16x32 stage has 32 tiles and stays with k_conv.  (The pixel count of the blind-spot case (3, 9, True, 4, 64).)
+    ((3, 3, False, 16, 32, 64, 0, 1), dict(first="k_conv_thin", cdma=[(32, 64)], cus=256)),
+    # a persistent grid of 6 workgroups: the weight-gradient kernel's multi-tile prefetch and K-step schedule with TW != TH
+    ((3, 3, False, 2, 64, 32, 6, 1), dict(first="k_conv", cdma=[], wgrad_multi=True)),
+]
+TF_CASES = [_hw_case(*(c[:4] + (c[4],) + c[4:]), None) for c in CASES] + [_hw_case(*c, e) for c, e in HW_CASES]
+TF_CASES = [pytest.param(*t.values, id=t.id.rsplit("-", 1)[0]) for t in TF_CASES]          # (the expectation is not part of a case's name)
+PROF_FAMILY = {0: "k_conv", 1: "k_conv", 2: "k_conv", 4: "k_gdma", 5: "k_cdma", 6: "k_cdma"}
+
+
 @pytest.fixture
 def conv_mode_reset():
     yield
     from ssdn.hip import lib as L
     L.load().ssdn_conv_set_mode(1)
+    for kind in PROF_FAMILY:
+        L.load().ssdn_profile_enable(kind, 0)
 
 
-@pytest.mark.parametrize("cin,cout,bs,B,P,cus_plan,conv_mode", CASES)
-def test_every_op_teacher_forced(cin, cout, bs, B, P, cus_plan, conv_mode, conv_mode_reset):
+def _launch_counts(lib):
+    """launches per kernel family since the last call (the library's in-stream profiler, bench.py's roofline leg)"""
+    import ctypes as C
+    from ssdn.hip import lib as L
+    out = {}
+    for kind, fam in PROF_FAMILY.items():
+        ms, n, fl, by = C.c_double(), C.c_longlong(), C.c_double(), C.c_double()
+        L.check(lib.ssdn_profile_read(kind, C.byref(ms), C.byref(n), C.byref(fl), C.byref(by)))
+        out[fam] = out.get(fam, 0) + n.value
+    return out
+
+
+@pytest.mark.parametrize("cin,cout,bs,B,H,W,cus_plan,conv_mode,expect", TF_CASES)
+def test_every_op_teacher_forced(cin, cout, bs, B, H, W, cus_plan, conv_mode, expect, conv_mode_reset):
     from ssdn.hip.engine import DeviceNet, OpList, current_stream
     from ssdn.hip.graph import NetPlan
     from ssdn.hip import lib as L
     L.check(L.load().ssdn_conv_set_mode(conv_mode))
     cus = cus_plan or L.load().ssdn_device_cus()
     p = R.make_params(cin, cout, bs, seed=7)
-    plan = NetPlan("m/", cin, cout, bs, B, P, P, cus=cus, dev_cus=L.load().ssdn_device_cus())
+    plan = NetPlan("m/", cin, cout, bs, B, H, W, cus=cus, dev_cus=L.load().ssdn_device_cus())
     flat = flat_params(plan, p)
     it = Interp(plan, flat, fp16=True)
-    it.t["m/in32"] = R.hash_tensor((B, cin, P, P), 91, 0, 1)
+    it.t["m/in32"] = R.hash_tensor((B, cin, H, W), 91, 0, 1)
     it.run(plan.pack)
     it.run(plan.fwd)
-    it.t["m/g32"] = R.hash_tensor((B, cout, P, P), 92, -1, 1) * 1e-3
+    it.t["m/g32"] = R.hash_tensor((B, cout, H, W), 92, -1, 1) * 1e-3
     it.run(plan.bwd)
+    served = []                                  # (op index, role, layer, H, W, tiling, kc, kernel family) of every conv op, when asked for
+    if expect is not None:
+        for kind in PROF_FAMILY:
+            L.check(L.load().ssdn_profile_enable(kind, 8))
 
     dparams = flat.to(dev())
     dgrads = torch.zeros_like(dparams)
@@ -230,6 +284,11 @@ def test_every_op_teacher_forced(cin, cout, bs, B, P, cus_plan, conv_mode, conv_
             dn.t[op.a["route"]].fill_(-1)
         OpList([rec]).run(current_stream())
         torch.cuda.synchronize()
+        if expect is not None and op.type == "conv":
+            n = {k: v for k, v in _launch_counts(L.load()).items() if v}
+            # (k_conv_thin carries no counter: it is the only other kernel csrc/conv_mfma.hip::launch_conv dispatches to)
+            fam = "+".join(sorted(n)) if n else "k_conv_thin"
+            served.append((i, op.a["role"], op.a["layer"], op.a["H"], op.a["W"], (1 << op.a["ltn"], 1 << op.a["lth"], 1 << op.a["ltw"]), op.a["kc"], fam))
         if op.type == "conv" and op.a.get("urot") is not None:
             # fused UNROT_FWD: the rows the one-row shift leaves empty are not the launch's to write (they stay as they were: zero
             # in the zero-initialised tensor of a real run, NaN here); everything else is compared below
@@ -318,9 +377,39 @@ def test_every_op_teacher_forced(cin, cout, bs, B, P, cus_plan, conv_mode, conv_
             dn.t[dst.t][..., dst.co + c_lo:dst.co + ch] = ref.to(dev()).to(dn.t[dst.t].dtype)
         i += 1
     os.makedirs(OUTDIR, exist_ok=True)
-    with open(os.path.join(OUTDIR, "teacher_forced_%d_%d_%d_%d_%d_cus%d_mode%d.txt" % (cin, cout, int(bs), B, P, cus_plan, conv_mode)), "w") as f:
+    size = "%d" % H if H == W else "%dx%d" % (H, W)
+    with open(os.path.join(OUTDIR, "teacher_forced_%d_%d_%d_%d_%s_cus%d_mode%d.txt" % (cin, cout, int(bs), B, size, cus_plan, conv_mode)), "w") as f:
         f.write("\n".join(failures) if failures else "all %d ops OK\n" % len(ops))
+        for r in served:
+            f.write("op %d conv %s %s %dx%d tile (TN, TH, TW) %s kc %d: %s\n" % r)
+        if expect is not None:
+            import ctypes as C
+            for k, op in enumerate(ops):
+                if op.type == "wgrad":
+                    v = (C.c_int32 * 9)()
+                    inst = L.load().ssdn_wgrad_variant(C.byref(dn._mat(op)[1]), v)
+                    f.write("op %d wgrad %s %dx%d tile (TN, TH, TW) %s tiles %d mega %d: instance %d variant (thin, MT, CPW, NL, BOTH, PS, KS, RWX, RWD) %s\n" % (
+                        k, op.a["layer"], op.a["H"], op.a["W"], (1 << op.a["ltn"], 1 << op.a["lth"], 1 << op.a["ltw"]), _wgrad_tiles(op.a),
+                        op.a.get("mega", 0), inst, list(v)))
     assert not failures, "\n".join(failures[:40])
+    if expect is not None:
+        # the case reached the kernels it is there for
+        if "cus" in expect and L.load().ssdn_device_cus() != expect["cus"]:
+            return                                # (the default size rule is stated for the CU count of an MI355X)
+        first = [r for r in served if r[1] == "fwd" and r[2] == "encode_block_1.0"]
+        assert [r[7] for r in first] == [expect["first"]], first
+        got = sorted({(r[3], r[4]) for r in served if "k_cdma" in r[7]}, reverse=True)
+        assert got == sorted(expect["cdma"], reverse=True), "stages served by k_cdma: %s" % got
+        for r in served:        # ... by k_cdma alone, every 3x3 layer of such a stage but those k_conv_thin takes
+            if (r[3], r[4]) in expect["cdma"] and r[7] != "k_conv_thin" and next(l for l in plan.layers if l.name == r[2]).k == 3:
+                assert r[7] == "k_cdma", r
+        if expect.get("wgrad_multi"):
+            multi = [op.a["layer"] for op in ops if op.type == "wgrad" and _wgrad_tiles(op.a) > cus and op.a["ltw"] != op.a["lth"]]
+            assert len(multi) >= 4, "weight-gradient ops whose workgroups own several tiles with TW != TH: %s" % multi
+
+
+def _wgrad_tiles(a):
+    return -(-a["W"] >> a["ltw"]) * -(-a["H"] >> a["lth"]) * -(-a["N"] >> a["ltn"])
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -456,8 +545,19 @@ def test_full_size_config2_properties():
     assert not bad, "\n".join(bad)
 
 
-@pytest.mark.parametrize("B,P,mode", [(2, 32, "all"), (32, 64, "all"), (2, 32, None), (4, 64, "buckets"), (32, 64, "split"), (4, 128, "split")])
-def test_merged_weight_gradient_launch_is_bit_identical(B, P, mode, monkeypatch):
+# (cin, cout, blindspot, B, H, W, mode).  The plain cases at 32x64: the tile walk of every block of the merged launch with H != W (tiles of
+# 8x16 and 16x16 pixels on stages 32x64 ... 1x2); "all" = every op an entry of k_wgrad_mega, None = k_wgrad_multi for the small layers
+MERGED_WGRAD_CASES = [(3, 9, True, 2, 32, 32, "all"), (3, 9, True, 32, 64, 64, "all"), (3, 9, True, 2, 32, 32, None), (3, 9, True, 4, 64, 64, "buckets"),
+                      (3, 9, True, 32, 64, 64, "split"), (3, 9, True, 4, 128, 128, "split"), (3, 3, False, 4, 32, 64, "all"), (3, 3, False, 4, 32, 64, None)]
+
+
+def _merged_case(cin, cout, bs, B, H, W, mode):
+    name = "%d-%d-%s" % (B, H, mode) if bs else "%d-%d-%s-%d-%dx%d-%s" % (cin, cout, bs, B, H, W, mode)    # (the blind-spot cases keep their names)
+    return pytest.param(cin, cout, bs, B, H, W, mode, id=name)
+
+
+@pytest.mark.parametrize("cin,cout,bs,B,H,W,mode", [_merged_case(*c) for c in MERGED_WGRAD_CASES])
+def test_merged_weight_gradient_launch_is_bit_identical(cin, cout, bs, B, H, W, mode, monkeypatch):
     """A run of consecutive SSDN_OP_WGRAD ops executes as ONE launch -- the chip-wide k_wgrad_mega (csrc/wgrad_mega.hip: one workgroup
     per CU works through a list of blocks of several ops' grids) or, for round 3's per-layer plans, k_wgrad_multi for the small layers;
     every block runs the code of its own op's launch, so the gradients must equal those of one-op-at-a-time execution bit for bit."""
@@ -469,7 +569,7 @@ def test_merged_weight_gradient_launch_is_bit_identical(B, P, mode, monkeypatch)
     monkeypatch.setattr(G, "WGRAD_MEGA", mode)
     monkeypatch.setattr(G, "MEGA_MIN_PX", 0)                  # (the small fixture too)
     dev = torch.device("cuda:0")
-    plan = NetPlan("m/", 3, 9, True, B, P, P, cus=L.load().ssdn_device_cus())
+    plan = NetPlan("m/", cin, cout, bs, B, H, W, cus=L.load().ssdn_device_cus())
     g = torch.Generator(device="cpu").manual_seed(11)
     flat = (torch.randn(plan.nparams, generator=g) * 0.05).to(dev)
     dn = DeviceNet(plan, dev, flat, torch.zeros_like(flat))
@@ -493,7 +593,11 @@ def test_merged_weight_gradient_launch_is_bit_identical(B, P, mode, monkeypatch)
 
     one_by_one = run([OpList([r]) for r in recs])           # a run of one op is never merged
     merged = run([OpList(recs)])
-    if mode:
+    if mode and not bs:
+        # (that every op has an instance in the chip-wide launch is a statement about the BASELINE plans; here the merged launch must be exercised)
+        nmerge = sum(1 for r in recs if L.load().ssdn_wgrad_mega_ok(C.byref(r[1])) == 1)
+        assert nmerge >= 8, "the fixture must exercise the merged launch (%d ops with an instance in it)" % nmerge
+    elif mode:
         nmerge = sum(1 for r in recs if L.load().ssdn_wgrad_mega_ok(C.byref(r[1])))
         assert nmerge == len(recs), "every op of the BASELINE plan must have an instance in the chip-wide launch (%d of %d)" % (nmerge, len(recs))
     else:
@@ -507,16 +611,34 @@ def test_merged_weight_gradient_launch_is_bit_identical(B, P, mode, monkeypatch)
     assert torch.equal(merged[:n], again[:n]), "the merged launch must be reproducible bit for bit"
 
 
-def _longest_chain(lib, ol):
-    """longest run of ops the library executes as one k_conv_chain launch, over all start positions of the list"""
+def _longest_chain(lib, ol, sizes=False):
+    """longest run of ops the library executes as one k_conv_chain launch, over all start positions of the list (sizes: and the (H, W) of
+    the SSDN_OP_CONV ops of that run)"""
     import ctypes as C
     from ssdn.hip import lib as L
-    best = 0
+    best, at = 0, 0
     for i in range(ol.n):
         n = lib.ssdn_chain_len(C.byref(ol.arr, i * C.sizeof(L.OpRec)), ol.n - i)
         assert n >= 0, lib.ssdn_last_error().decode()
-        best = max(best, n)
-    return best
+        if n > best:
+            best, at = n, i
+    if not sizes:
+        return best
+    convs = [C.cast(ol.arr[k].args, C.POINTER(L.ConvArgs)).contents for k in range(at, at + best) if ol.arr[k].type == L.OP["conv"]]
+    return best, [(a.H, a.W) for a in convs]
+
+
+def _check_chain_reached(lib, ol, need):
+    """need: the least length of the longest chain (the square cases), or, for H != W -- where the chain takes whole-image tiles with N a
+    multiple of 256 / pixels per image, so how far it reaches depends on the shape -- "hw": a conv with H != W inside it, "hw256": and one
+    with H * W == 256 (conv_chain.hip::chain_conv_ok's rule for the 48-channel layers)"""
+    n, sizes = _longest_chain(lib, ol, sizes=True)
+    if isinstance(need, int):
+        assert n >= need, "the fixture must exercise the chained launch"
+        return
+    assert n >= 2 and any(h != w for h, w in sizes), "the chained launch must hold a layer with H != W: %d ops, convs %s" % (n, sizes)
+    if need == "hw256":
+        assert any(h != w and h * w == 256 for h, w in sizes), "the chained launch must hold a 256-pixel layer with H != W: %s" % sizes
 
 
 @pytest.fixture
@@ -526,10 +648,18 @@ def conv_chain_reset():
     L.load().ssdn_conv_set_chain(1)
 
 
-# (cin, cout, blindspot, B, P, layers the chain must cover): 4 x B images; the chain starts at the first layer whose images have
+# (cin, cout, blindspot, B, H, W, layers the chain must cover): 4 x B images; the chain starts at the first layer whose images have
 # <= 64 pixels and whose max-pool the planner fused into the conv (whole-image tiles: N a multiple of 256 / pixels per image)
-@pytest.mark.parametrize("cin,cout,bs,B,P,min_chain", [(3, 9, True, 4, 64, 7), (3, 9, True, 8, 32, 2), (3, 3, False, 16, 64, 7), (1, 2, True, 32, 64, 7)])
-def test_conv_chain_is_bit_identical(cin, cout, bs, B, P, min_chain, conv_chain_reset):
+# 16 x 32x64: the chain holds the 4x8 and 2x4 stages (8x16 is the 128 pixels chain_conv_ok excludes); 16 x 128x32: the smallest shape whose
+# chain holds a 256-pixel stage with H != W (32x8), down to 4x1
+CHAIN_FWD_CASES = [(3, 9, True, 4, 64, 64, 7), (3, 9, True, 8, 32, 32, 2), (3, 3, False, 16, 64, 64, 7), (1, 2, True, 32, 64, 64, 7),
+                   (3, 3, False, 16, 32, 64, "hw"), (3, 3, False, 16, 128, 32, "hw256")]
+CHAIN_BWD_CASES = [(3, 9, True, 4, 64, 64, 9), (3, 9, True, 8, 32, 32, 3), (3, 3, False, 16, 64, 64, 9), (1, 2, True, 32, 64, 64, 9),
+                   (3, 3, False, 16, 32, 64, "hw"), (3, 3, False, 16, 128, 32, "hw256")]
+
+
+@pytest.mark.parametrize("cin,cout,bs,B,H,W,min_chain", [_hw_case(*c) for c in CHAIN_FWD_CASES])
+def test_conv_chain_is_bit_identical(cin, cout, bs, B, H, W, min_chain, conv_chain_reset):
     """A run of consecutive small forward layers executes as ONE launch with the activations resident in LDS (k_conv_chain,
     csrc/conv_chain.hip); every tensor the separate launches would have written -- each layer's output and each fused max-pool
     output -- must come out bit for bit the same."""
@@ -539,14 +669,14 @@ def test_conv_chain_is_bit_identical(cin, cout, bs, B, P, min_chain, conv_chain_
     from ssdn.hip.graph import NetPlan
     lib = L.load()
     dev = torch.device("cuda:0")
-    plan = NetPlan("m/", cin, cout, bs, B, P, P, cus=lib.ssdn_device_cus())
+    plan = NetPlan("m/", cin, cout, bs, B, H, W, cus=lib.ssdn_device_cus())
     g = torch.Generator(device="cpu").manual_seed(5)
     flat = (torch.randn(plan.nparams, generator=g) * 0.08).to(dev)
     dn = DeviceNet(plan, dev, flat, torch.zeros_like(flat))
     dn.t["m/in32"].copy_(torch.rand(dn.t["m/in32"].shape, generator=g).to(dev))
     dn.pack.run(current_stream())
     recs = [dn._mat(op) for op in plan.fwd]
-    assert _longest_chain(lib, OpList(recs)) >= min_chain, "the fixture must exercise the chained launch"
+    _check_chain_reached(lib, OpList(recs), min_chain)
 
     def run_fwd(chain):
         L.check(lib.ssdn_conv_set_chain(int(chain)))
@@ -567,8 +697,8 @@ def test_conv_chain_is_bit_identical(cin, cout, bs, B, P, min_chain, conv_chain_
     assert not bad, "tensors that differ between the chained and the separate launches: %s" % bad
 
 
-@pytest.mark.parametrize("cin,cout,bs,B,P,min_chain", [(3, 9, True, 4, 64, 9), (3, 9, True, 8, 32, 3), (3, 3, False, 16, 64, 9), (1, 2, True, 32, 64, 9)])
-def test_backward_chain_is_bit_identical(cin, cout, bs, B, P, min_chain, conv_chain_reset):
+@pytest.mark.parametrize("cin,cout,bs,B,H,W,min_chain", [_hw_case(*c) for c in CHAIN_BWD_CASES])
+def test_backward_chain_is_bit_identical(cin, cout, bs, B, H, W, min_chain, conv_chain_reset):
     """The data gradients of the small layers -- with their fused epilogues (LeakyReLU' mask, skip-gradient add, fused up-sampling
     adjoint) and the max-pool backward ops between them -- execute as ONE launch (k_conv_chain<true>); every gradient tensor of the
     backward pass and the flat parameter gradient must come out bit for bit as from the separate launches."""
@@ -577,7 +707,7 @@ def test_backward_chain_is_bit_identical(cin, cout, bs, B, P, min_chain, conv_ch
     from ssdn.hip.graph import NetPlan
     lib = L.load()
     dev = torch.device("cuda:0")
-    plan = NetPlan("m/", cin, cout, bs, B, P, P, cus=lib.ssdn_device_cus())
+    plan = NetPlan("m/", cin, cout, bs, B, H, W, cus=lib.ssdn_device_cus())
     g = torch.Generator(device="cpu").manual_seed(6)
     flat = (torch.randn(plan.nparams, generator=g) * 0.08).to(dev)
     dn = DeviceNet(plan, dev, flat, torch.zeros_like(flat))
@@ -586,7 +716,7 @@ def test_backward_chain_is_bit_identical(cin, cout, bs, B, P, min_chain, conv_ch
     dn.fwd.run(current_stream())
     dn.t["m/g32"].copy_((torch.randn(dn.t["m/g32"].shape, generator=g) * 1e-3).to(dev))
     dn.t["m/gmax"][0] = int(np.float32(dn.t["m/g32"].abs().max().item()).view(np.int32))
-    assert _longest_chain(lib, dn.bwd) >= min_chain, "the fixture must exercise the chained launch"
+    _check_chain_reached(lib, dn.bwd, min_chain)
 
     def run_bwd(chain):
         L.check(lib.ssdn_conv_set_chain(int(chain)))

@@ -17,28 +17,41 @@ def flat_params(plan, p):
     return flat
 
 
+def _hw_case(*c):
+    """a case written (..., B, H, W, ...): the id of a square one stays the one it had when the cases carried one size P"""
+    i = next(k for k, v in enumerate(c) if isinstance(v, bool)) + 2        # H follows (cin, cout, blindspot, B)
+    sq = c[i] == c[i + 1]
+    return pytest.param(*c, id="-".join(str(v) for v in (c[:i + 1] + c[i + 2:] if sq else c[:i] + ("%dx%d" % c[i:i + 2],) + c[i + 2:])))
+
+
 # dev_cus = 8: the plan of a device with 8 CUs, on which the full-resolution layers of these small cases already have >= one tile per CU --
 # the fusions of the BASELINE sizes (decode_block_1.2 storing un-rotated + sign bytes, UPSUM_BWD in the data gradients) are lowered
-@pytest.mark.parametrize("cin,cout,bs,B,P,dev_cus", [(3, 9, True, 2, 32, None), (1, 2, True, 1, 32, None), (3, 3, False, 2, 32, None),
-                                                     (3, 1, False, 1, 64, None), (3, 9, True, 2, 32, 8), (1, 2, True, 1, 64, 8)])
-def test_forward_backward_lowering(cin, cout, bs, B, P, dev_cus):
+# H != W (plain network only; the blind-spot plan refuses it): 32x64 and 64x32 are the smallest transposed pair (stages down to 1x2 / 2x1),
+# 32x96 and 96x64 have a side of 3 at the bottom stage, which no power-of-two tile divides
+LOWERING_CASES = [(3, 9, True, 2, 32, 32, None), (1, 2, True, 1, 32, 32, None), (3, 3, False, 2, 32, 32, None),
+                  (3, 1, False, 1, 64, 64, None), (3, 9, True, 2, 32, 32, 8), (1, 2, True, 1, 64, 64, 8),
+                  (3, 3, False, 2, 32, 64, None), (3, 1, False, 1, 64, 32, 8), (1, 1, False, 3, 32, 96, None), (3, 3, False, 1, 96, 64, 8)]
+
+
+@pytest.mark.parametrize("cin,cout,bs,B,H,W,dev_cus", [_hw_case(*c) for c in LOWERING_CASES])
+def test_forward_backward_lowering(cin, cout, bs, B, H, W, dev_cus):
     """float64 on both sides: in fp32 a handful of activations within 1e-7 of zero flip the LeakyReLU branch between two
     summation orders, which hides real bugs behind a 1e-3 noise floor; in fp64 the lowering must agree to ~1e-12."""
     torch.set_default_dtype(torch.float64)
     try:
-        _check_lowering(cin, cout, bs, B, P, dev_cus)
+        _check_lowering(cin, cout, bs, B, H, W, dev_cus)
     finally:
         torch.set_default_dtype(torch.float32)
 
 
-def _check_lowering(cin, cout, bs, B, P, dev_cus=None):
+def _check_lowering(cin, cout, bs, B, H, W, dev_cus=None):
     p = {k: v.double() for k, v in R.make_params(cin, cout, bs, seed=7).items()}
-    plan = NetPlan("m/", cin, cout, bs, B, P, P, cus=8, dev_cus=dev_cus)
+    plan = NetPlan("m/", cin, cout, bs, B, H, W, cus=8, dev_cus=dev_cus)
     if dev_cus and bs:
         assert not any(op.type == "unrot_fwd" for op in plan.fwd) and any(op.a.get("urot") is not None for op in plan.fwd if op.type == "conv")
         assert "m/d1b" not in plan.tensors
     it = Interp(plan, flat_params(plan, p), fp16=False)
-    x = R.hash_tensor((B, cin, P, P), 91, 0, 1).double()
+    x = R.hash_tensor((B, cin, H, W), 91, 0, 1).double()
     it.t["m/in32"] = x.clone()
     it.run(plan.pack)
     it.run(plan.fwd)
@@ -46,7 +59,7 @@ def _check_lowering(cin, cout, bs, B, P, dev_cus=None):
     ref = R.net_forward(leaves, x, bs)
     np.testing.assert_allclose(it.t["m/out32"].numpy(), ref.detach().numpy(), rtol=1e-9, atol=1e-11)
     # backward: arbitrary upstream gradient
-    g = R.hash_tensor((B, cout, P, P), 92, -1, 1).double() * 1e-3
+    g = R.hash_tensor((B, cout, H, W), 92, -1, 1).double() * 1e-3
     (ref * g).sum().backward()
     it.t["m/g32"] = g.clone()
     it.run(plan.bwd)
@@ -57,6 +70,15 @@ def _check_lowering(cin, cout, bs, B, P, dev_cus=None):
         sc = float(rw.abs().max()) + 1e-12
         np.testing.assert_allclose(gw.numpy(), rw.numpy(), rtol=1e-8, atol=1e-10 * sc, err_msg=l.name)
         np.testing.assert_allclose(gb.numpy(), rb.numpy(), rtol=1e-8, atol=1e-10 * (float(rb.abs().max()) + 1e-12), err_msg=l.name)
+
+
+@pytest.mark.parametrize("H,W", [(32, 64), (64, 32)])
+def test_blindspot_plan_refuses_non_square_input(H, W):
+    """the rotation stack of the blind-spot network puts the four rotations of an image into one batch: H != W stays a ValueError at plan
+    time (and the plain network of the same shape plans)"""
+    with pytest.raises(ValueError, match="blind-spot mode needs square inputs"):
+        NetPlan("m/", 3, 9, True, 2, H, W, cus=8)
+    NetPlan("m/", 3, 3, False, 2, H, W, cus=8)
 
 
 def _validate_with_library(op):
@@ -87,19 +109,36 @@ def _validate_with_library(op):
     assert 0 <= rc <= 160 * 1024, (op.type, a["layer"], rc, L.load().ssdn_last_error())
 
 
+# the shapes of tests/test_hip_ops.py::HW_CASES as (cin, cout, B, H, W, cus): what the GPU tests run must be plannable and accepted here first
+NONSQUARE_TRAIN_SHAPES = [(3, 3, 2, 32, 64, 256), (3, 3, 2, 64, 32, 256), (3, 1, 1, 32, 128, 256), (1, 1, 3, 128, 32, 256), (3, 3, 2, 64, 96, 256),
+                          (3, 3, 1, 96, 64, 256), (3, 3, 16, 32, 64, 256), (3, 3, 2, 64, 32, 6), (3, 3, 16, 128, 32, 256), (3, 3, 4, 32, 64, 256),
+                          (3, 3, 2, 32, 64, 6), (1, 1, 3, 32, 96, 8), (3, 3, 1, 96, 64, 3)]
+# plain-network validation batches of a training run (ssdn/train.py builds the validation set with square=cfg[BLINDSPOT]): BSD and Kodak
+# images in both orientations, padded to multiples of 32, at batch 1
+NONSQUARE_EVAL_SHAPES = [(3, 3, 1, 352, 512, 256), (3, 3, 1, 512, 352, 256), (3, 3, 1, 512, 768, 256), (3, 3, 1, 768, 512, 256),
+                         (1, 1, 1, 352, 512, 256), (3, 3, 1, 64, 96, 256), (3, 3, 1, 96, 64, 256)]
+
+
 def test_plan_tilings_fit_lds():
-    """every conv / wgrad tiling of the BASELINE configurations is accepted by the library and fits the 160 KiB LDS of a CU"""
+    """every conv / wgrad tiling of the BASELINE configurations -- and of the plain network at H != W: the test shapes and the validation
+    shapes of an N2C / N2N / N2V training run -- is accepted by the library and fits the 160 KiB LDS of a CU"""
     from ssdn.hip.graph import LDS_LIMIT
     # (the small CU counts make workgroups own several tiles at small sizes: multi-tile prefetch constraints, output split)
-    for (cin, cout, bs, B, P, cus) in [(3, 9, True, 32, 64, 256), (3, 9, True, 16, 128, 256), (3, 3, False, 32, 64, 256),
-                                       (1, 1, False, 4, 32, 256), (3, 9, True, 2, 768, 256), (3, 9, True, 2, 512, 256),
-                                       (3, 9, True, 2, 32, 8), (3, 3, False, 2, 64, 6), (1, 2, True, 1, 32, 3), (3, 9, True, 1, 32, 1),
-                                       (3, 9, True, 4, 64, 16), (3, 9, True, 2, 96, 256), (3, 9, True, 8, 64, 64)]:
-        plan = NetPlan("m/", cin, cout, bs, B, P, P, cus=cus, train=P <= 128)
+    square = [(3, 9, True, 32, 64, 256), (3, 9, True, 16, 128, 256), (3, 3, False, 32, 64, 256),
+              (1, 1, False, 4, 32, 256), (3, 9, True, 2, 768, 256), (3, 9, True, 2, 512, 256),
+              (3, 9, True, 2, 32, 8), (3, 3, False, 2, 64, 6), (1, 2, True, 1, 32, 3), (3, 9, True, 1, 32, 1),
+              (3, 9, True, 4, 64, 16), (3, 9, True, 2, 96, 256), (3, 9, True, 8, 64, 64)]
+    cases = [(cin, cout, bs, B, P, P, cus, P <= 128) for (cin, cout, bs, B, P, cus) in square]
+    cases += [(cin, cout, False, B, H, W, cus, True) for (cin, cout, B, H, W, cus) in NONSQUARE_TRAIN_SHAPES]
+    cases += [(cin, cout, False, B, H, W, cus, False) for (cin, cout, B, H, W, cus) in NONSQUARE_EVAL_SHAPES]
+    for (cin, cout, bs, B, H, W, cus, train) in cases:
+        plan = NetPlan("m/", cin, cout, bs, B, H, W, cus=cus, train=train)
+        nchecked = 0
         for op in plan.fwd + plan.bwd:
             a = op.a
             if op.type in ("conv", "wgrad"):
                 _validate_with_library(op)
+                nchecked += 1
             if op.type == "conv":
                 padT = max(0, -min(t[0] for t in a["taps"])); padB = max(0, max(t[0] for t in a["taps"]))
                 padL = max(0, -min(t[1] for t in a["taps"])); padR = max(0, max(t[1] for t in a["taps"]))
@@ -107,6 +146,7 @@ def test_plan_tilings_fit_lds():
                 lds = NP * (a["kc"] * 2 + 16) + 2 * min(3, a["Mpad"] // 32) * 32 * (a["kc"] * 2 + 16)
                 assert lds <= LDS_LIMIT
                 assert a["ltw"] + a["lth"] + a["ltn"] <= 8
+        assert nchecked >= len(plan.layers) * (3 if train else 1) - 2, (cin, cout, bs, B, H, W, cus, nchecked)
 
 
 def test_every_baseline_weight_gradient_op_has_an_instance_in_the_chip_wide_launch():
