@@ -71,7 +71,8 @@ enum ssdn_op_type {
     SSDN_OP_INPUT_GRAD = 22,   /* gradient w.r.t. the network input (NoiseNetwork under autograd with x.requires_grad) */
     SSDN_OP_HEAD_VJP = 23,     /* vector-Jacobian product of the SSDN head: any upstream gradient of LOSS / posterior mean / mu */
     SSDN_OP_MSE_VJP = 24,      /* the same for the (masked) MSE pipelines: LOSS / network output */
-    SSDN_OP_ACCUM = 25         /* dst[i] = fl(dst[i] + src[i]): folds a per-pass staging value into a running gradient sum */
+    SSDN_OP_ACCUM = 25,        /* dst[i] = fl(dst[i] + src[i]): folds a per-pass staging value into a running gradient sum */
+    SSDN_OP_HEAD_POSTERIOR = 26 /* per-pixel posterior of the SSDN head beyond its mean: covariance, std maps, samples (no planned list holds it) */
 };
 
 /* One record of the op list.  `args` points at the matching ssdn_*_args struct (host memory).
@@ -552,6 +553,35 @@ typedef struct ssdn_noise_args {
     int32_t n2v_radius;   /* sub-patch radius (2 for the reference's 5 x 5) */
     uint64_t seed, offset;
 } ssdn_noise_args;
+
+/* ---- SSDN_OP_HEAD_POSTERIOR --------------------------------------------------------------------
+ * The per-pixel posterior N(pme, Sigma_post) the head of SSDN_OP_HEAD_SSDN implies (impulse: a two-component mixture), beyond its mean:
+ * csrc/head_posterior.hip, DESIGN.md section 3.13.  net_out, noisy, noise_param, est_raw, B, C, H, W, style, mode, diag, nchunks are
+ * ssdn_head_args' (the same sigma_c, alpha, est and Sigma_x = U U^T rules).  Sigma_post is the matrix M with pme = M (Sx'^-1 mu + Sn'^-1 y)
+ * in the form that arm of the head evaluates (e = 1e-6):
+ *   full, C = 3: K Sn' symmetrised, K = Sx' T^-1, Sx' = Sigma_x + e I, Sn' = diag(sigma_c^2) + e I, T = Sx' + Sn';  C = 1: sx sn / sy;
+ *   diag = 1, C = 3: diag(1 / (1/(sx_c + e) + 1/(sn_c + e) + e));  style 2: (1 - w) Sigma_x + w (1 - w) r r^T, r = y - mu_x, w the head's.
+ * Outputs (any may be NULL, not all): cov [B, C(C+1)/2, H, W], upper triangle in the order 00, 01, 02, 11, 12, 22 (C = 1: [B,1,H,W]);
+ *   std [B,C,H,W] = sqrt(max(diagonal, 0));  samples [n_samples, B, C, H, W]: pme + L z with L L^T = Sigma_post (Cholesky, pivots clamped
+ *   at 0); style 2: y exactly with probability w, else mu_x + U z.  Random numbers: Philox4x32-10 keyed by `seed`, counter = (b H W + pixel,
+ *   0x80000000 + 2 s + k, offset): sample s is a pure function of (seed, offset, s, b, pixel) -- independent of n_samples and nchunks --
+ *   and shares no stream with SSDN_OP_NOISE.  B H W < 2^32.  Adding this op changed no existing struct: the ABI version stays.
+ * Argument errors are raised before any device call (text prefixed "head_posterior:"); diag = 1 with style 2 is an error. */
+typedef struct ssdn_head_posterior_args {
+    const float* net_out; /* [B,Cout,H,W] */
+    const float* noisy;   /* [B,C,H,W] */
+    const float* noise_param;
+    const float* est_raw;
+    int32_t B, C, H, W;
+    int32_t style, mode;
+    int32_t diag;
+    int32_t nchunks;
+    float* cov;
+    float* std;
+    float* samples;
+    int32_t n_samples;    /* >= 1 when samples is given */
+    uint64_t seed, offset;
+} ssdn_head_posterior_args;
 
 /* ---- SSDN_OP_INPUT_GRAD --------------------------------------------------------------------
  * replaces: the data gradient autograd propagates into the network input through the first conv (noise_network.py:69-71) and the

@@ -785,28 +785,14 @@ int launch_adam(const ssdn_adam_args* a, hipStream_t s) {
 // Random numbers are counter-based (Philox4x32-10): the value of element e of stream s of launch `offset` is a pure function of
 // (seed, offset, s, e), so the Noise2Void replacement can RE-DERIVE the noisy value of the neighbour it copies (no second pass).
 // ------------------------------------------------------------------------------------------------
-struct Ph4 { unsigned v[4]; };
-static __device__ __forceinline__ Ph4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const unsigned hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const unsigned n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    Ph4 o;
-    o.v[0] = c0; o.v[1] = c1; o.v[2] = c2; o.v[3] = c3;
-    return o;
-}
-static __device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * (1.f / 16777216.f) + (0.5f / 16777216.f); }   // (0, 1)
+#include "philox.h"        // Ph4, philox4x32_10, u01, ph_normal
 enum { NS_INPUT = 0, NS_REF = 1, NS_PARAM = 2, NS_COORD = 3, NS_PARAM_REF = 4 };
 // noisy value of element e (channel plane index bc = b*C + c) of realisation `stream`
 static __device__ __forceinline__ float noise_apply(const ssdn_noise_args& a, float clean, float param, unsigned e, unsigned stream) {
     const Ph4 r = philox4x32_10(e, stream, (unsigned)a.offset, (unsigned)(a.offset >> 32), (unsigned)a.seed, (unsigned)(a.seed >> 32));
     float v;
     if (a.style == 0) {
-        const float z = sqrtf(-2.f * __logf(u01(r.v[0]))) * __cosf(6.28318530718f * u01(r.v[1]));      // Box-Muller
+        const float z = ph_normal(r.v[0], r.v[1]);      // Box-Muller
         v = clean + param * z;
     } else {
         // Poisson(1) by inversion: P(k) = e^-1 / k!

@@ -366,6 +366,30 @@ class Denoiser(nn.Module):
             out[PipelineOutput.LOSS] = pick(PipelineOutput.LOSS, eng.loss)
         return out
 
+    def posterior(self, data, samples: int = 0, seed: int = 0, offset: int = 0) -> Dict:
+        """The per-pixel posterior of the SSDN head for a BCHW batch (or a pipeline `data` list): N(mean, cov) per pixel, for the impulse
+        model the two-component mixture's mean and covariance.  -> {"mean": IMG_DENOISED [B,C,H,W], "cov": [B, C(C+1)/2, H, W] (upper
+        triangle: 00, 01, 02, 11, 12, 22), "std": [B,C,H,W]} and, for samples > 0, "samples": [samples, B, C, H, W] posterior draws -- a
+        pure function of (seed, offset, sample index, pixel), so pass a fresh offset for fresh draws.  Runs an inference plan under
+        no_grad whatever the module's mode: it never becomes the forward that backward() / optimizer_step() / accumulate_metrics() act
+        on.  Plain, fresh tensors; nothing is differentiable.  SSDN pipeline only."""
+        if self._pipeline != Pipeline.SSDN:
+            raise NotImplementedError("Denoiser.posterior: the %s pipeline has no posterior covariance (SSDN pipeline only)" % self._pipeline.value)
+        samples = int(samples)
+        if samples < 0:
+            raise ValueError("samples must be >= 0")
+        if isinstance(data, Tensor):
+            data = [data]
+        keep = (self._last_engine, getattr(self, "_has_loss_last", None))
+        try:
+            with torch.no_grad():
+                out = self._run(data, clone=True)           # (no_grad: an inference plan; _last_train_engine is left alone)
+                res = {k: v.clone() for k, v in self._last_engine.posterior(n_samples=samples, seed=seed, offset=offset).items()}
+        finally:
+            self._last_engine, self._has_loss_last = keep
+        res["mean"] = out[PipelineOutput.IMG_DENOISED]
+        return res
+
     def backward(self):
         """Run the planned backward pass of the last training-mode run_pipeline; gradients land in `flat_grad` and are
         visible as `.grad` of every parameter."""

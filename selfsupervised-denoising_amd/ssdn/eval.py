@@ -30,6 +30,8 @@ class DenoiserEvaluator(DenoiserTrainer):
             self.denoiser = Denoiser.from_state_dict(sd)
         self.cfg = self.denoiser.cfg
         self._run_dir = run_dir
+        # `ssdn eval --posterior N`: None = off; N >= 0: per image of the first pass, the posterior std map and N posterior samples
+        self.posterior_samples = None
         self.init_state()
 
     def evaluate(self):
@@ -61,6 +63,8 @@ class DenoiserEvaluator(DenoiserTrainer):
             if remaining > 0:
                 self.save_image_outputs(outputs, os.path.join(self.run_dir_path, "eval_imgs"), "img_{index:05}_{desc}.png",
                                         batch_indexes=range(min(remaining, n)))
+                if self.posterior_samples is not None:
+                    self.save_posterior_outputs(outputs, output_0_index, range(min(remaining, n)))
             with open(os.path.join(self.run_dir_path, "psnrs.csv"), "a") as f:
                 if output_0_index == 0:
                     f.write(",".join(["id", "psnr_nsy"] + list(self.img_outputs(prefix="psnr").values())) + "\n")
@@ -71,3 +75,22 @@ class DenoiserEvaluator(DenoiserTrainer):
                 for i in range(n):
                     f.write(",".join(["{:04d}".format(output_0_index + i)] + ["{:.4f}".format(float(v[i])) for v in values]) + "\n")
         return callback
+
+    def save_posterior_outputs(self, outputs: Dict, output_0_index: int, batch_indexes) -> None:
+        """`posterior/img_{index:05}_std.npy` (float32 [C,h,w], un-padded, upright) and `posterior/img_{index:05}_sample{k}.png` for the
+        images `eval_imgs/` gets: Denoiser.posterior of the batch just evaluated (its own inference run; the seed is fixed and the offset
+        is the batch's first index, so a repeated evaluation draws the same samples)."""
+        import numpy as np
+        data = outputs[PipelineOutput.INPUTS]
+        metadata = data[NoisyDataset.METADATA]
+        post = self.denoiser.posterior(data, samples=self.posterior_samples, seed=0, offset=output_0_index)
+        out_dir = os.path.join(self.run_dir_path, "posterior")
+        os.makedirs(out_dir, exist_ok=True)
+        std = post["std"].cpu()
+        smp = post["samples"].cpu() if self.posterior_samples else None
+        for bi in batch_indexes:
+            stem = os.path.join(out_dir, "img_{index:05}".format(index=int(metadata[NoisyDataset.Metadata.INDEXES][bi])))
+            # (the dataset classes hand out tensors with H and W swapped, utils/data.py: swapped back here as tensor2image does)
+            np.save(stem + "_std.npy", NoisyDataset.unpad(std, metadata, bi).permute(0, 2, 1).contiguous().numpy().astype(np.float32))
+            for k in range(self.posterior_samples):
+                ssdn.utils.save_tensor_image(NoisyDataset.unpad(smp[k], metadata, bi), stem + "_sample{}.png".format(k))

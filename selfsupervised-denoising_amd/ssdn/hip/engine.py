@@ -562,6 +562,7 @@ class DenoiserEngine:
         self.gen = 0
         self.g_fresh = self.loss_fwd = False
         self._vjp = None
+        self._post = {}             # posterior(): cov / std / samples buffers, allocated on first use (no plan tensor)
 
     # ---- op construction -----------------------------------------------------------------------------------
     def _gmax(self, net: Optional[DeviceNet]):
@@ -810,6 +811,38 @@ class DenoiserEngine:
             self.gen += 1
             self.g_fresh = self.loss_fwd = False
         self.main.fwd.run(s)
+
+    def posterior(self, n_samples: int = 0, seed: int = 0, offset: int = 0, cov: bool = True, std: bool = True, stream=None):
+        """The per-pixel posterior of the LAST forward beyond its mean (SSDN_OP_HEAD_POSTERIOR, csrc/head_posterior.hip): one launch on the
+        engine's stream behind that forward, reading its net_out, input and noise estimate.  -> dict of "cov" [B, C(C+1)/2, H, W], "std"
+        [B,C,H,W] and, for n_samples > 0, "samples" [n_samples, B, C, H, W]: the engine's own buffers, allocated on first use outside the
+        plan's tensors and overwritten by the next call (an exported plan knows nothing of them).  Nothing here is differentiable."""
+        if self.pipeline != "ssdn":
+            raise NotImplementedError("the posterior covariance exists for the ssdn pipeline only")
+        n_samples = int(n_samples)
+        if n_samples < 0:
+            raise ValueError("n_samples must be >= 0")
+        if not (cov or std or n_samples):
+            raise ValueError("posterior: nothing requested")
+        B, Cn, H, W = self.B, self.C, self.H, self.W
+        f32 = dict(dtype=torch.float32, device=self.device)
+        buf = self._post
+        if cov and "cov" not in buf:
+            buf["cov"] = torch.zeros((B, Cn * (Cn + 1) // 2, H, W), **f32)
+        if std and "std" not in buf:
+            buf["std"] = torch.zeros((B, Cn, H, W), **f32)
+        if n_samples and ("samples" not in buf or buf["samples"].shape[0] != n_samples):
+            buf["samples"] = torch.zeros((n_samples, B, Cn, H, W), **f32)
+        if self.mode == "var":
+            est_ptr = _ptr(self.est_raw)
+        else:
+            est_ptr = _ptr(self.params, 4 * self.est_off) if self.mode == "const" else None
+        a = L.HeadPosteriorArgs(_ptr(self.main.tensor("out32")), _ptr(self.inp), _ptr(self.noise_param), est_ptr, B, Cn, H, W,
+                                STYLE[self.style], MODE[self.mode], int(self.diag), self.nchunks,
+                                _ptr(buf["cov"]) if cov else None, _ptr(buf["std"]) if std else None,
+                                _ptr(buf["samples"]) if n_samples else None, n_samples, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1))
+        OpList([("head_posterior", a)]).run(current_stream() if stream is None else stream)
+        return {k: buf[k] for k, on in (("cov", cov), ("std", std), ("samples", n_samples > 0)) if on}
 
     def _head_addend(self, on: bool) -> None:
         """input_grad engines: whether the first network input gradient of the sum adds the head term the VJP left in `dx`"""

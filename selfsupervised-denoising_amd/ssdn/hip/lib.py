@@ -17,7 +17,7 @@ MAX_TAPS = 9
 OP = dict(pack_input=1, conv=2, pool_fwd=3, pool_bwd=4, upsum_bwd=5, unrot_fwd=6, unrot_bwd=7, wgrad=8, wreduce=9,
           wpack=10, grad_pack=11, head_ssdn=12, head_final=13, spatial_mean=14, mse=15, mask_mse=16, adam=17,
           metrics=18, zero=19, event_record=20, noise=21, input_grad=22, head_vjp=23,
-          mse_vjp=24, accum=25)
+          mse_vjp=24, accum=25, head_posterior=26)
 
 i32, f32, vp = C.c_int32, C.c_float, C.c_void_p
 
@@ -145,11 +145,18 @@ class AccumArgs(C.Structure):
     _fields_ = [("dst", vp), ("src", vp), ("n", C.c_int64)]
 
 
+class HeadPosteriorArgs(C.Structure):
+    _fields_ = [("net_out", vp), ("noisy", vp), ("noise_param", vp), ("est_raw", vp), ("B", i32), ("C", i32), ("H", i32), ("W", i32),
+                ("style", i32), ("mode", i32), ("diag", i32), ("nchunks", i32), ("cov", vp), ("std", vp), ("samples", vp),
+                ("n_samples", i32), ("seed", C.c_uint64), ("offset", C.c_uint64)]
+
+
 ARG_TYPES = dict(pack_input=PackInputArgs, conv=ConvArgs, pool_fwd=PoolArgs, pool_bwd=PoolArgs, upsum_bwd=UpsumArgs,
                  unrot_fwd=UnrotArgs, unrot_bwd=UnrotArgs, wgrad=WgradArgs, wreduce=WreduceArgs, wpack=WpackArgs,
                  grad_pack=GradPackArgs, head_ssdn=HeadArgs, head_final=HeadFinalArgs, spatial_mean=SpatialMeanArgs,
                  mse=MseArgs, mask_mse=MseArgs, adam=AdamArgs, metrics=MetricsArgs, zero=ZeroArgs, event_record=EventArgs, noise=NoiseArgs,
-                 input_grad=InputGradArgs, head_vjp=HeadVjpArgs, mse_vjp=MseVjpArgs, accum=AccumArgs)
+                 input_grad=InputGradArgs, head_vjp=HeadVjpArgs, mse_vjp=MseVjpArgs, accum=AccumArgs,
+                 head_posterior=HeadPosteriorArgs)
 
 # every symbol include/ssdn_hip.h declares
 ABI_VERSION = 19      # SSDN_ABI_VERSION of include/ssdn_hip.h this binding mirrors
