@@ -48,7 +48,7 @@ class Interp:
         self.grads = torch.zeros_like(self.params)
         self.t = {}
         self.scale = 1.0
-        self.slab = self.bslab = None
+        self.slabs, self.bslabs = {}, {}      # slab tensor name -> one block per mblock of its weight-gradient launch (any legal order of the list runs)
         self.L = {l.name: l for l in plan.layers}
 
     # ---- tensor access ---------------------------------------------------------------------------------
@@ -261,7 +261,7 @@ class Interp:
     def op_wgrad(self, layer, dz, src0, src1, c0, c1, up0, N, H, W, taps, coff, M, Mpad, Ktot, Kpad, nslabs, ltw, lth, ltn,
                  slab=None, bslab=None, csplit=0, mblocks=1, kreal=0, mega=0, cost=0.0, **_planner_private):
         x = _r16(self._gather(src0, src1, c0, c1, up0, N, H, W), self.fp16, "bf16")   # staged as bf16 on the device
-        self.slabs, self.bslabs = [], []
+        self.slabs[slab], self.bslabs[bslab] = [], []
         for mb in range(mblocks):        # a merged launch covers mblocks blocks of M output channels of the dz view
             g = self.t[dz.t][..., dz.co + mb * M:dz.co + mb * M + M]
             sl = torch.zeros(len(taps), Mpad, Kpad)
@@ -270,21 +270,20 @@ class Interp:
                 sl[t, :M, :kw] = torch.einsum("nhwm,nhwk->mk", g, self._shift(x, dy, dx)[..., coff[t]:coff[t] + kw])
             bs = torch.zeros(Mpad)
             bs[:M] = g.sum((0, 1, 2))
-            self.slabs.append(sl)
-            self.bslabs.append(bs)
-        self.slab, self.bslab = self.slabs[0], self.bslabs[0]
+            self.slabs[slab].append(sl)
+            self.bslabs[bslab].append(bs)
 
     def op_wreduce(self, layer, nslabs, ntaps, M, Mpad, Kpad, cin, cin_full, m_off, c_off, with_bias, tapblock=0,
                    slab=None, bslab=None, mblock=0):
-        self.slab, self.bslab = self.slabs[mblock], self.bslabs[mblock]
+        sl, bsl = self.slabs[slab][mblock], self.bslabs[bslab][mblock]
         l = self.L[layer]
         base = self.plan.param_base
         gw = self.grads[base + l.w_off: base + l.w_off + l.M * l.cin * l.ntaps].reshape(l.M, l.cin, l.ntaps)
         assert cin_full == l.cin
         if tapblock:     # the slab's taps are channel blocks of a 1x1 layer
-            blk = self.slab[:, :M, :].permute(1, 0, 2).reshape(M, ntaps * Kpad)[:, :cin]
+            blk = sl[:, :M, :].permute(1, 0, 2).reshape(M, ntaps * Kpad)[:, :cin]
             gw[m_off:m_off + M, c_off:c_off + cin, 0] = blk / self.scale
         else:
-            gw[m_off:m_off + M, c_off:c_off + cin, :] = self.slab[:, :M, :cin].permute(1, 2, 0) / self.scale
+            gw[m_off:m_off + M, c_off:c_off + cin, :] = sl[:, :M, :cin].permute(1, 2, 0) / self.scale
         if with_bias:
-            self.grads[base + l.b_off + m_off: base + l.b_off + m_off + M] = self.bslab[:M] / self.scale
+            self.grads[base + l.b_off + m_off: base + l.b_off + m_off + M] = bsl[:M] / self.scale

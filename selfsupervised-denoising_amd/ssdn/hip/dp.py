@@ -24,10 +24,12 @@ program order.  NOTE: scaling across GPUs has not been measured on hardware by t
 from __future__ import annotations
 
 import os
-from typing import Callable, List, Optional, Sequence, Set, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
+
+from .graph import bucket_layers, bucket_ranges  # noqa: F401  (pure functions of the layer offsets: they live with the planner; re-exported)
 
 
 def env_world() -> Tuple[int, int, int]:
@@ -63,25 +65,7 @@ def shard_rows(global_batch: int, rank: int, world: int) -> Tuple[int, int]:
     return rank * per, (rank + 1) * per
 
 
-def bucket_ranges(layers, n_main: int, n_total: int) -> List[Tuple[int, int]]:
-    """Contiguous [lo,hi) ranges of the flat buffer in backward completion order."""
-    off = {l.name: l.w_off for l in layers}
-    return [(off["output_block.0"], n_main), (off["decode_block_1.0"], off["output_block.0"]),
-            (off["decode_block_5.0"], off["decode_block_1.0"]), (0, off["decode_block_5.0"])] + \
-        ([(n_main, n_total)] if n_total > n_main else [])
-
-
 N_MAIN_BUCKETS = 4
-
-
-def bucket_layers(layers, split_head: bool = True) -> List[Set[str]]:
-    """Layer names of the main-net buckets of `bucket_ranges`, same order: head | dec1 | dec2..dec5 | encoder.  split_head=False:
-    head and dec1 as one set (the three reduction runs of the per-layer plans, engine._group_reductions_lanes)."""
-    off = {l.name: l.w_off for l in layers}
-    h, a, b = off["output_block.0"], off["decode_block_1.0"], off["decode_block_5.0"]
-    head, dec1 = {l.name for l in layers if l.w_off >= h}, {l.name for l in layers if a <= l.w_off < h}
-    rest = [{l.name for l in layers if b <= l.w_off < a}, {l.name for l in layers if l.w_off < b}]
-    return ([head, dec1] if split_head else [head | dec1]) + rest
 
 
 class GradExchange:

@@ -1,6 +1,7 @@
 """Device side of the op-list plans: owns the HBM buffers (allocated through torch, used as a plain device allocator),
 materialises `ssdn.hip.graph` Op records into the C structs of include/ssdn_hip.h and executes them with ONE call
-into libssdn_hip.so per phase (forward / backward / optimiser).  No torch compute op is on this path.
+into libssdn_hip.so per phase (forward / backward / optimiser).  No torch compute op is on this path.  Order and lanes of
+the backward list are the planner's (NetPlan.bwd_sched); here the list is only cut (input gradient, deferred tail) and marked (events).
 """
 from __future__ import annotations
 
@@ -12,6 +13,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import lib as L
+from .dp import N_MAIN_BUCKETS, bucket_layers
 from .graph import NetPlan, Op, View
 
 
@@ -22,26 +24,14 @@ def _ptr(t: torch.Tensor, byte_off: int = 0) -> int:
 class OpList:
     """A materialised op list: a ctypes array of ssdn_op plus the argument structs it points to."""
 
-    # weight-gradient GEMMs / slab reductions run on the library's side streams.  (The executor also offers lane 3, a second
-    # weight-gradient lane; alternating the GEMMs between lanes 1 and 3 measured 4 % SLOWER: two of these kernels, each
-    # sized to own every CU, only thrash each other's LDS-resident pipelines.)
-    # The slab reduction follows its GEMM on the same lane: every cross-lane dependency is a hipEventRecord on the producing
-    # stream, which costs that stream ~5-10 us of bubble -- a separate reduction lane (2) measured 4.5 % slower.
-    LANE = {"wgrad": (1,), "wreduce": (1,)}
-
-    def __init__(self, recs, lanes: bool = False):
+    def __init__(self, recs):
+        """recs: (type, args) or (type, args, lane) -- lane 0, the main lane, where none is given"""
         self.args = [r[1] for r in recs]                      # keep the structs alive
         self.arr = (L.OpRec * max(1, len(recs)))()
-        count = {}
         for i, r in enumerate(recs):
-            ty, a = r[0], r[1]
-            self.arr[i].type = L.OP[ty]
-            choices = self.LANE.get(ty, (0,)) if lanes else (0,)
-            self.arr[i].lane = choices[count.get(ty, 0) % len(choices)]
-            if lanes and len(r) > 2:                      # (type, args, lane): the planner chose the lane of this record itself
-                self.arr[i].lane = r[2]
-            count[ty] = count.get(ty, 0) + 1
-            self.arr[i].args = C.cast(C.pointer(a), C.c_void_p)
+            self.arr[i].type = L.OP[r[0]]
+            self.arr[i].lane = r[2] if len(r) > 2 else 0
+            self.arr[i].args = C.cast(C.pointer(r[1]), C.c_void_p)
         self.n = len(recs)
 
     def run(self, stream: int = 0):
@@ -71,7 +61,10 @@ class DeviceNet:
             # shift of the un-rotation leaves empty are never written by the fused SSDN_OP_UNROT_FWD (ssdn_conv_args.urot): they ARE these zeros
             self.t[name] = torch.zeros(spec.shape, dtype=self.DT[spec.kind], device=device)
         self.fwd = OpList([self._mat(op) for op in plan.fwd])
-        self._bwd_recs, self._bwd_layers = self._group_reductions(plan, [self._mat(op) for op in plan.bwd])
+        # the backward list in the planner's execution order (plan.bwd_sched): (type, args, lane), and the layer of every slab reduction
+        recs = [self._mat(op) for op in plan.bwd]
+        self._bwd_recs = [recs[i] + (lane,) for i, lane in plan.bwd_sched]
+        self._bwd_layers = [plan.bwd[i].a["layer"] if plan.bwd[i].type == "wreduce" else None for i, _ in plan.bwd_sched]
         # the SSDN_OP_INPUT_GRAD record of an input-gradient plan (its owner may set the addend); hold_input_grad: the op leaves the
         # backward list and runs as `input_grad_ops` where the owner enqueues it (behind a term computed on another stream)
         k = next((i for i, r in enumerate(self._bwd_recs) if r[0] == "input_grad"), None)
@@ -81,7 +74,7 @@ class DeviceNet:
             self.input_grad_ops = OpList([self._bwd_recs[k][:2]])
             del self._bwd_recs[k]
             del self._bwd_layers[k]
-        self.bwd = OpList(self._bwd_recs, lanes=True)
+        self.bwd = OpList(self._bwd_recs)
         # the last gradient bucket's slab reductions close the list: a training step may run them in front of its optimiser launch
         # instead (DeviceEngine.backward(defer_tail=True)): [weight-gradient lane: wait for the main lane's last launch, two
         # reduction launches] -> join -> Adam becomes join -> reductions -> Adam on ONE stream (one cross-lane hop less in the serial tail)
@@ -89,7 +82,7 @@ class DeviceNet:
         while ntail < len(self._bwd_recs) and self._bwd_recs[len(self._bwd_recs) - 1 - ntail][0] == "wreduce":
             ntail += 1
         self.tail_recs = [(r[0], r[1]) for r in self._bwd_recs[len(self._bwd_recs) - ntail:]] if 0 < ntail < len(self._bwd_recs) else []
-        self.bwd_head = OpList(self._bwd_recs[:len(self._bwd_recs) - len(self.tail_recs)], lanes=True) if self.tail_recs else None
+        self.bwd_head = OpList(self._bwd_recs[:len(self._bwd_recs) - len(self.tail_recs)]) if self.tail_recs else None
         self.pack = OpList([self._mat(op) for op in plan.pack])
         self.accumulate = False
 
@@ -111,7 +104,7 @@ class DeviceNet:
         lane, each on that lane right behind the bucket's last reduction THERE, and its collective waits for all of them
         (one mark on the lane of the last reduction in LIST order left the other lane's writes unordered).
         Marks that fall on the same (point of the list, lane) share one event."""
-        lane_of = lambda r: r[2] if len(r) > 2 else OpList.LANE.get(r[0], (0,))[0]     # noqa: E731  (what OpList(lanes=True) assigns)
+        lane_of = lambda r: r[2]                               # noqa: E731  (the scheduled lane)
         last = {}                                              # (bucket, lane) -> index of the bucket's last reduction on that lane
         for i, name in enumerate(self._bwd_layers):
             if name is None:
@@ -133,7 +126,7 @@ class DeviceNet:
                 if idx == i:
                     recs.append(("event_record", L.EventArgs(new_event(sorted(ks))), lane))
                     self.marks.append((len(recs) - 1, lane, sorted(ks)))
-        ol = OpList(recs, lanes=True)
+        ol = OpList(recs)
         # buckets whose LAST marks sit at the same point of the list complete together: the exchange may merge their collectives
         done_at = {}
         for (idx, lane), ks in marks.items():
@@ -145,175 +138,6 @@ class DeviceNet:
         ol.coincident = [sorted(ks) for _, ks in sorted(by_pos.items())]
         ol.marks = list(self.marks)
         return ol
-
-    @staticmethod
-    def _order_mega(plan, recs):
-        """Backward list of a plan whose weight gradients run as chip-wide launches (graph.WGRAD_MEGA): the main-lane ops in the
-        planner's order; the SSDN_OP_WGRAD records of a launch group consecutive (the executor runs such a run as ONE k_wgrad_mega
-        launch), placed behind the main-lane op that produces the group's last gradient operand, directly followed by the group's
-        slab reductions (a run of reductions is two launches).  A group that would fall inside a run of chainable main-lane ops
-        (k_conv_chain) waits behind the run.  Returns (records, layer name of each record if it is a reduction else None)."""
-        side = lambda op: op.type in ("wgrad", "wreduce")   # noqa: E731
-        gof = lambda op: plan.wgrad_group_of(op.a["layer"], plan.is_skip_half(op))  # noqa: E731
-        flush = {}
-        for i, op in enumerate(plan.bwd):
-            if op.type == "wgrad":
-                flush[gof(op)] = i
-        lane_of = {}
-        for g in list(flush):
-            _, lane, after = plan.wgrad_group_info(g)
-            lane_of[g] = MEGA_LANE if lane is None else lane
-            if after is not None:              # behind that layer's data-gradient launch (never in front of the group's last operand)
-                at = [i for i, op in enumerate(plan.bwd) if op.type == "conv" and op.a["role"] == "dgrad" and op.a["layer"] == after]
-                if at:
-                    flush[g] = max(flush[g], at[0])
-        def chainable(op):
-            if op.type == "conv":
-                px = op.a["H"] * op.a["W"]
-                thin = px == 256 and op.a["Mpad"] <= 64 and op.a["Ktot"] <= 48 and op.a.get("upsum") is None
-                return op.a["role"] == "dgrad" and len(op.a["taps"]) == 9 and (px <= 64 or thin)
-            return op.type == "pool_bwd" and (op.a["H"] // 2) * (op.a["W"] // 2) <= 256
-        windows, cur = [], None
-        for i, op in enumerate(plan.bwd):
-            if chainable(op):
-                cur = [i, i] if cur is None else [cur[0], i]
-            elif not side(op) and cur is not None:
-                windows.append(cur)
-                cur = None
-        if cur is not None:
-            windows.append(cur)
-        for first, end in windows:
-            for g in flush:
-                if first <= flush[g] < end:
-                    flush[g] = end
-        out, names = [], []
-        for i, (op, rec) in enumerate(zip(plan.bwd, recs)):
-            if not side(op):
-                out.append(rec)
-                names.append(None)
-            for g in sorted(flush):
-                if flush[g] != i:
-                    continue
-                for op2, rec2 in zip(plan.bwd, recs):
-                    if op2.type == "wgrad" and gof(op2) == g:
-                        out.append((rec2[0], rec2[1], lane_of[g]))
-                        names.append(None)
-                for op2, rec2 in zip(plan.bwd, recs):
-                    if op2.type == "wreduce" and gof(op2) == g:
-                        out.append((rec2[0], rec2[1], lane_of[g]))
-                        names.append(op2.a["layer"])
-        return out, names
-
-    @staticmethod
-    def _group_reductions(plan, recs):
-        if getattr(plan, "_mega_ops", None):
-            return DeviceNet._order_mega(plan, recs)
-        return DeviceNet._group_reductions_lanes(plan, recs)
-
-    @staticmethod
-    def _group_reductions_lanes(plan, recs):
-        """Move every slab reduction to the end of its reduction run (ssdn.hip.dp.bucket_layers(split_head=False): head+dec1 | dec2..dec5 |
-        encoder): the executor merges a run of consecutive SSDN_OP_WREDUCE ops into two launches, instead of two launches per
-        layer (51 latency-bound launches, 0.52 ms per step in situ).  Legal: every weight-gradient launch owns its slab and
-        the flat gradient is only read after the backward list.  Returns (records, layer name of each record if it is a
-        reduction else None)."""
-        from .dp import bucket_layers
-        if not plan.bwd:
-            return recs, [op.a.get("layer") if op.type == "wreduce" else None for op in plan.bwd]
-        buckets = bucket_layers(plan.layers, split_head=False)
-        bucket_of = {name: k for k, b in enumerate(buckets) for name in b}
-        # The weight-gradient GEMMs of the layers at 16x16 pixels and below are issued together, where the last of them
-        # stood: the executor runs a run of consecutive small SSDN_OP_WGRAD ops as ONE launch (k_wgrad_multi; same rule as
-        # csrc/wgrad_mfma.hip::wgrad_mergeable).  Legal for the same reason: a side-lane op may always be delayed.
-        from .graph import WGRAD_SMALL_PX
-        small = lambda op: op.type == "wgrad" and op.a["N"] * op.a["H"] * op.a["W"] <= WGRAD_SMALL_PX  # noqa: E731
-        # (one run per gradient bucket, so that a bucket still completes where it did)
-        flush_at = {}                                   # index of the last small wgrad of each bucket
-        for i, op in enumerate(plan.bwd):
-            if small(op):
-                flush_at[bucket_of[op.a["layer"]]] = i
-        nsmall = {k: sum(1 for op in plan.bwd if small(op) and bucket_of[op.a["layer"]] == k) for k in flush_at}
-        flush_at = {k: i for k, i in flush_at.items() if nsmall[k] > 1}
-        grouped = lambda op: small(op) and bucket_of[op.a["layer"]] in flush_at  # noqa: E731
-        last = {}
-        for i, op in enumerate(plan.bwd):
-            if op.type in ("wgrad", "wreduce"):
-                k = bucket_of[op.a["layer"]]
-                last[k] = max(last.get(k, -1), flush_at[k] if grouped(op) else i)
-        # The main-lane ops on images of <= 64 pixels (data gradients, max-pool backward) run as ONE launch when they are consecutive
-        # in the list (k_conv_chain, csrc/conv_chain.hip: the library's rule): side-lane records that would fall between them are
-        # emitted behind the last of them (a side-lane op may always be delayed).
-        def chainable(op):
-            if op.type == "conv":
-                px = op.a["H"] * op.a["W"]
-                thin = px == 256 and op.a["Mpad"] <= 64 and op.a["Ktot"] <= 48 and op.a.get("upsum") is None
-                return op.a["role"] == "dgrad" and len(op.a["taps"]) == 9 and (px <= 64 or thin)
-            return op.type == "pool_bwd" and (op.a["H"] // 2) * (op.a["W"] // 2) <= 256
-        windows, cur = [], None
-        for i, op in enumerate(plan.bwd):
-            if chainable(op):
-                cur = [i, i] if cur is None else [cur[0], i]
-            elif op.type not in ("wgrad", "wreduce") and cur is not None:
-                windows.append(cur)
-                cur = None
-        if cur is not None:
-            windows.append(cur)
-        for first, end in windows:
-            for d in (flush_at, last):
-                for k in d:
-                    if first <= d[k] < end and (CHAIN_POSTPONES is None or k in CHAIN_POSTPONES):
-                        d[k] = end
-        out, names, pending = [], [], {k: [] for k in range(len(buckets))}
-        pending_small = {k: [] for k in range(len(buckets))}
-        pending_main = {k: [] for k in range(len(buckets))}
-        # SSDN_OP_GRAD_PACK and the narrow net_out layer's data gradient behind it are ONE launch when adjacent (csrc/gradpack_dgrad.hip): the
-        # weight-gradient record the planner puts between them waits behind the pair (it needs the pair's output anyway)
-        hold_to, held = -1, []
-        if plan.bwd[0].type == "grad_pack":
-            j = next((k for k in range(1, len(plan.bwd)) if plan.bwd[k].type not in ("wgrad", "wreduce")), -1)
-            if j > 1 and plan.bwd[j].type == "conv" and plan.bwd[j].a["role"] == "dgrad" and len(plan.bwd[j].a["taps"]) == 1 and plan.bwd[j].a["Ktot"] == 16:
-                hold_to = j
-        for i, (op, rec) in enumerate(zip(plan.bwd, recs)):
-            if op.type == "wreduce":
-                pending[bucket_of[op.a["layer"]]].append((rec, op.a["layer"]))
-            elif op.type == "wgrad" and op.a["layer"] in MAIN_LANE_WGRADS:
-                pending_main[bucket_of[op.a["layer"]]].append((rec[0], rec[1], 0))
-            elif grouped(op):
-                pending_small[bucket_of[op.a["layer"]]].append(rec)
-            elif op.type == "wgrad" and i < hold_to:
-                held.append(rec)
-            else:
-                out.append(rec)
-                names.append(None)
-                if i == hold_to:
-                    out += held
-                    names += [None] * len(held)
-                    held = []
-            for k in sorted(set(flush_at) | set(last)):          # bucket by bucket: a bucket's merged launch, then its reductions
-                if flush_at.get(k) == i:
-                    out += pending_small[k]
-                    names += [None] * len(pending_small[k])
-                    pending_small[k] = []
-                if not SPLIT_SMALL_RUNS:
-                    continue
-                if last.get(k) == i:
-                    out += pending_main[k]
-                    names += [None] * len(pending_main[k])
-                    pending_main[k] = []
-                    for rec_k, name_k in pending[k]:
-                        out.append(rec_k)
-                        names.append(name_k)
-                    pending[k] = []
-            for k in sorted(last):
-                if last[k] == i and not SPLIT_SMALL_RUNS:
-                    out += pending_main[k]
-                    names += [None] * len(pending_main[k])
-                    pending_main[k] = []
-                    for rec_k, name_k in pending[k]:
-                        out.append(rec_k)
-                        names.append(name_k)
-                    pending[k] = []
-        return out, names
 
     # ---- helpers ------------------------------------------------------------------------------------------
     def tensor(self, short: str) -> torch.Tensor:
@@ -443,29 +267,11 @@ class DeviceNet:
         raise ValueError("unknown op type " + op.type)
 
 
-# Weight-gradient GEMMs that run on the MAIN lane, after the last data-gradient launch of their gradient bucket, instead of the
-# weight-gradient lane: the backward pass ends with lane 1 still working through its queue (150 us) while lane 0 has nothing left.
-# Measured on the bench workload (tools/ab_lanes.py, same process, with the chained small layers): encode_block_1.0 alone 2.031 ms
-# per step (2.056 with none), with encode_block_1.2 1.985, with encode_block_2.0 instead 2.005, all three 2.034.  Same kernels,
-# same slabs: bit-identical.
-MAIN_LANE_WGRADS = ("encode_block_1.0", "encode_block_1.2")
-# True: when the merged small-layer launches of two gradient buckets end up next to each other in the list, the first bucket's
-# reductions go between them (two k_wgrad_multi launches); False: one launch for both, then both buckets' reductions.
-SPLIT_SMALL_RUNS = True
 # Denoiser.train_step without a gradient exchange leaves the last bucket's slab reductions to the optimiser call (DeviceEngine.backward)
 DEFER_TAIL = True
-# Gradient buckets whose side-lane records are moved behind a run of chainable main-lane ops (None: all).  Moving the decoder
-# bucket's merged weight-gradient launch behind the whole run makes ONE chain of 12 ops, but that launch then waits for the end of the
-# chain; leaving it where the bucket's last gradient appears makes two chains (3 + 9 ops) and starts it ~100 us earlier.
-CHAIN_POSTPONES = (2,)          # measured (tools/ab_lanes.py, same process): all buckets 1.975 ms per step, the encoder bucket only 1.959, none 1.965
-
 # Pixels of one sample a workgroup of the loss-head kernel walks (256 threads): 1024 = four pixels per thread in sequence.  (One pixel per
 # thread used to be slower, 33 vs 20 us, because every WAVE ended with an atomic on the gradient sentinel; the kernel now issues one per block.)
 HEAD_PX_PER_BLOCK = 1024
-
-# Lane of the chip-wide weight-gradient launches and their slab reductions (graph.WGRAD_MEGA).  A workgroup of those launches owns its
-# CU, one per CU: next to them nothing else runs, so they sit on the main lane (0), behind the data gradients whose results they read.
-MEGA_LANE = 0
 
 STYLE = {"gauss": 0, "poisson": 1, "impulse": 2}
 MODE = {"known": 0, "const": 1, "var": 2}
@@ -875,7 +681,7 @@ class DenoiserEngine:
             return
         self._tail_pending = False
         if exchange is not None and exchange.overlapped:
-            from .dp import bucket_layers, N_MAIN_BUCKETS as NB
+            NB = N_MAIN_BUCKETS
             if getattr(self, "_bwd_ev_key", None) != id(exchange):
                 exchange.reset_marks()
                 self._bwd_ev = self.main.bwd_with_events(bucket_layers(self.main.plan.layers), exchange.new_event)

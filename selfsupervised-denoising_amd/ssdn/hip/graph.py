@@ -12,7 +12,7 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Set, Tuple
 
 LDS_LIMIT = 160 * 1024
 # conv tilings at or below this many bytes of LDS are preferred: two workgroups then share a CU, so one workgroup's
@@ -26,7 +26,7 @@ MID_WGRAD_PX, MID_WGRAD_G = 131072, 2       # the 32x32 stage: two column groups
 WGRAD_CU_FRAC = (3, 4)        # share of the CUs the persistent weight-gradient grids are planned for (see _wgrad)
 # Round 4: the weight gradients of a whole group of layers as ONE chip-wide launch (k_wgrad_mega, csrc/wgrad_mfma.hip): one
 # workgroup per CU, every op's grid sized by the cost model below so that all workgroups finish together.
-#   "all": one launch behind the last data gradient; "buckets": one per gradient bucket (ssdn.hip.dp.bucket_layers);
+#   "all": one launch behind the last data gradient; "buckets": one per gradient bucket (bucket_layers);
 #   None: round 3's per-layer launches on the side lane
 WGRAD_MEGA = "split"
 FUSE_UNROT_FWD = True         # decode_block_1.2 stores its output un-rotated (no SSDN_OP_UNROT_FWD launch, no d1b tensor) where k_cdma serves it
@@ -43,6 +43,28 @@ SPLIT_AFTER = "decode_block_2.2"   # "split": the side-lane launch is issued beh
                               # (measured, same process: behind decode_block_2.0's data gradient 1.6028 ms per step, behind decode_block_2.2's 1.5892, None 1.5864;
                               #  behind decode_block_2.2 only ONE of the eight k_cdma<3,*> launches of a step runs beside it, with None two)
 SPLIT_GROUP0 = ("output_block", "decode_block_2.2")   # "split": layers (name prefixes) of the side-lane launch
+# Lane of the chip-wide weight-gradient launches and their slab reductions (WGRAD_MEGA).  A workgroup of those launches owns its
+# CU, one per CU: next to them nothing else runs, so they sit on the main lane (0), behind the data gradients whose results they read.
+MEGA_LANE = 0
+# The side lane: the per-layer weight-gradient GEMMs / slab reductions and the "split" head launch run on this side stream of the
+# library.  (The executor also offers lane 3, a second weight-gradient lane; alternating the GEMMs between lanes 1 and 3 measured 4 %
+# SLOWER: two of these kernels, each sized to own every CU, only thrash each other's LDS-resident pipelines.)
+# The slab reduction follows its GEMM on the same lane: every cross-lane dependency is a hipEventRecord on the producing
+# stream, which costs that stream ~5-10 us of bubble -- a separate reduction lane (2) measured 4.5 % slower.
+WGRAD_LANE = 1
+# Weight-gradient GEMMs that run on the MAIN lane, after the last data-gradient launch of their gradient bucket, instead of the
+# weight-gradient lane: the backward pass ends with lane 1 still working through its queue (150 us) while lane 0 has nothing left.
+# Measured on the bench workload (tools/ab_lanes.py, same process, with the chained small layers): encode_block_1.0 alone 2.031 ms
+# per step (2.056 with none), with encode_block_1.2 1.985, with encode_block_2.0 instead 2.005, all three 2.034.  Same kernels,
+# same slabs: bit-identical.
+MAIN_LANE_WGRADS = ("encode_block_1.0", "encode_block_1.2")
+# True: when the merged small-layer launches of two gradient buckets end up next to each other in the list, the first bucket's
+# reductions go between them (two k_wgrad_multi launches); False: one launch for both, then both buckets' reductions.
+SPLIT_SMALL_RUNS = True
+# Gradient buckets whose side-lane records are moved behind a run of chainable main-lane ops (None: all).  Moving the decoder
+# bucket's merged weight-gradient launch behind the whole run makes ONE chain of 12 ops, but that launch then waits for the end of the
+# chain; leaving it where the bucket's last gradient appears makes two chains (3 + 9 ops) and starts it ~100 us earlier.
+CHAIN_POSTPONES = (2,)          # measured (tools/ab_lanes.py, same process): all buckets 1.975 ms per step, the encoder bucket only 1.959, none 1.965
 # cost model of one weight-gradient block, in cycles (calibrated on BASELINE config 2 with tools/wgrad_calib.py):
 #   K-step of 16 pixels = base + per_mfma * MT * CPW;  a block = tiles * ksteps * K-step + fixed + slab bytes / slab_rate
 MEGA_COST = {
@@ -158,6 +180,58 @@ def net_layers(in_channels: int, out_channels: int, blindspot: bool) -> List[Lay
 
 def net_param_count(layers: List[Layer]) -> int:
     return layers[-1].b_off + layers[-1].M
+
+
+def bucket_ranges(layers, n_main: int, n_total: int) -> List[Tuple[int, int]]:
+    """Contiguous [lo,hi) ranges of the flat buffer in backward completion order: the gradient buckets (ssdn.hip.dp)."""
+    off = {l.name: l.w_off for l in layers}
+    return [(off["output_block.0"], n_main), (off["decode_block_1.0"], off["output_block.0"]),
+            (off["decode_block_5.0"], off["decode_block_1.0"]), (0, off["decode_block_5.0"])] + \
+        ([(n_main, n_total)] if n_total > n_main else [])
+
+
+def bucket_layers(layers, split_head: bool = True) -> List[Set[str]]:
+    """Layer names of the main-net buckets of `bucket_ranges`, same order: head | dec1 | dec2..dec5 | encoder.  split_head=False:
+    head and dec1 as one set (the three reduction runs of the per-layer plans and the launch groups of WGRAD_MEGA = "buckets")."""
+    off = {l.name: l.w_off for l in layers}
+    h, a, b = off["output_block.0"], off["decode_block_1.0"], off["decode_block_5.0"]
+    head, dec1 = {l.name for l in layers if l.w_off >= h}, {l.name for l in layers if a <= l.w_off < h}
+    rest = [{l.name for l in layers if b <= l.w_off < a}, {l.name for l in layers if l.w_off < b}]
+    return ([head, dec1] if split_head else [head | dec1]) + rest
+
+
+SIDE_OPS = ("wgrad", "wreduce")     # the records the scheduler may delay (NetPlan._schedule); every other op keeps its place on the main lane
+
+
+def chainable(op: Op) -> bool:
+    """The library's rule (csrc/conv_chain.hip): main-lane ops on small images (data gradients, max-pool backward) that run as ONE
+    k_conv_chain launch when they are consecutive in the list."""
+    if op.type == "conv":
+        px = op.a["H"] * op.a["W"]
+        thin = px == 256 and op.a["Mpad"] <= 64 and op.a["Ktot"] <= 48 and op.a.get("upsum") is None
+        return op.a["role"] == "dgrad" and len(op.a["taps"]) == 9 and (px <= 64 or thin)
+    return op.type == "pool_bwd" and (op.a["H"] // 2) * (op.a["W"] // 2) <= 256
+
+
+def chain_runs(ops: List[Op]) -> List[Tuple[int, int]]:
+    """(first, last) index of every run of chainable main-lane ops of `ops` (csrc/conv_chain.hip merges a run into one launch); the
+    side-lane records between them do not end a run: the scheduler moves them out of it."""
+    runs, cur = [], None
+    for i, op in enumerate(ops):
+        if chainable(op):
+            cur = (i, i) if cur is None else (cur[0], i)
+        elif op.type not in SIDE_OPS and cur is not None:
+            runs.append(cur)
+            cur = None
+    return runs + ([cur] if cur is not None else [])
+
+
+def _behind_runs(at: Dict[int, int], runs, only=None) -> None:
+    """positions `at` (group -> index of the list) that fall inside a run of chainable ops move behind the run (groups in `only`; None: all)"""
+    for first, end in runs:
+        for k in at:
+            if first <= at[k] < end and (only is None or k in only):
+                at[k] = end
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -329,6 +403,9 @@ class NetPlan:
         self.pack: List[Op] = []
         self.max_slab = 0
         self.max_bslab = 0
+        self.bwd_sched: List[Tuple[int, int]] = []     # (index into bwd, lane) in execution order: what the engine materialises
+        self._mega_ops: list = []
+        self._plan_groups()
         self._build()
 
     # ---- helpers -------------------------------------------------------------------------------------------
@@ -419,7 +496,7 @@ class NetPlan:
                                        mblock=mb, slab=None, bslab=None))
                 self.bwd.append(r)
                 reds.append(r)
-            self._mega_ops = getattr(self, "_mega_ops", []) + [(op, reds)]
+            self._mega_ops.append((op, reds))
             return
 
         def candidate(G):
@@ -712,21 +789,33 @@ class NetPlan:
             b.append(Op("input_grad", dict(g_e0=View(g_e0), g_d1a=View(self.prefix + "g_d1a"), dst=dx32, B=B, C=C, H=H, W=W, R=self.R,
                                            taps=list(t3), layer_e="encode_block_1.0", layer_d="decode_block_1.0")))
         self._wgrad(L["encode_block_1.0"], View(g_e0), 48, None, 0, 0, View(x16), 16, C, N, H, W, t3)
-        if getattr(self, "_mega_ops", None):
+        if self._mega_ops:
             self._plan_mega()
+        self._schedule()
 
     # ---- chip-wide weight-gradient launches ------------------------------------------------------------------
+    def _plan_groups(self):
+        """Fix the chip-wide launch groups of this plan from the planner constants AS THEY ARE NOW (WGRAD_MEGA, SPLIT_*): nothing
+        reads them once the plan exists, so a plan materialises the same under whatever value a later plan is made with."""
+        mode = WGRAD_MEGA
+        buckets = bucket_layers(self.layers, split_head=False)
+        self._group_of, self._group_info = {}, {}
+        for l in self.layers:
+            for tag in ("/", "/skip"):
+                g = 0
+                if mode == "split":
+                    g = 0 if (l.name + tag).startswith(SPLIT_GROUP0) else 1
+                elif mode == "buckets":
+                    g = next(k for k, b in enumerate(buckets) if l.name in b)
+                self._group_of[l.name + tag] = g
+                self._group_info[g] = (self.cus, MEGA_LANE, None)
+        if mode == "split":
+            self._group_info[0] = (max(1, (self.cus * SPLIT_HEAD_CUS[0]) // SPLIT_HEAD_CUS[1]), WGRAD_LANE, SPLIT_AFTER)
+
     def wgrad_group_of(self, layer_name: str, skip_half: bool = False) -> int:
         """index of the chip-wide launch the weight gradients of `layer_name` belong to (WGRAD_MEGA).  skip_half: the op covers the
         skip-connection half of a decoder stage's first layer (its own SSDN_OP_WGRAD / SSDN_OP_WREDUCE pair: "<layer>/skip")."""
-        if WGRAD_MEGA == "split":
-            return 0 if (layer_name + ("/skip" if skip_half else "/")).startswith(SPLIT_GROUP0) else 1
-        if WGRAD_MEGA != "buckets":
-            return 0
-        off = {l.name: l.w_off for l in self.layers}
-        a, b = off["decode_block_1.0"], off["decode_block_5.0"]        # (== ssdn.hip.dp.bucket_layers)
-        w = off[layer_name]
-        return 0 if w >= a else (1 if w >= b else 2)
+        return self._group_of[layer_name + ("/skip" if skip_half else "/")]
 
     @staticmethod
     def is_skip_half(op) -> bool:
@@ -740,9 +829,7 @@ class NetPlan:
         at the start of the backward pass) run on HALF the CUs on the side lane next to the latency-bound bottom of the U (the
         16x16 layers and the chained 8x8..2x2 layers: ~270 us of launches that cannot fill the chip); everything else as one
         launch on all CUs behind the last data gradient."""
-        if WGRAD_MEGA == "split" and g == 0:
-            return max(1, (self.cus * SPLIT_HEAD_CUS[0]) // SPLIT_HEAD_CUS[1]), 1, SPLIT_AFTER
-        return self.cus, None, None
+        return self._group_info[g]
 
     @staticmethod
     def _thin_ok(a) -> bool:
@@ -862,3 +949,76 @@ class NetPlan:
                 a["bslab"] = self.T("bslab%d" % a["_id"], "f32", (mb * ns * a["Mpad"],))
                 for r in c["reds"]:
                     r.a["nslabs"], r.a["slab"], r.a["bslab"] = ns, a["slab"], a["bslab"]
+
+    # ---- the order and the lanes the device runs the backward list in ------------------------------------------------------------
+    def _schedule(self):
+        """bwd_sched: the main-lane ops in the data-flow order of `bwd`, every side record (SIDE_OPS) behind the op it is anchored
+        to.  A side record may always be delayed (every weight-gradient launch owns its slab, and the flat gradient is only read after
+        the list), never advanced.  _place_mega / _place_layers give each side record ((anchor, rank ...), lane): the anchor is the
+        index of bwd it is emitted behind, the rank orders the records of one anchor (group by group, weight gradients in front of
+        their reductions).  One sort emits the list: an op first (rank -2), then what is anchored to it."""
+        bwd = self.bwd
+        side = [i for i, op in enumerate(bwd) if op.type in SIDE_OPS]
+        place = (self._place_mega if self._mega_ops else self._place_layers)(side)
+        order = sorted(range(len(bwd)), key=lambda i: place[i][0] if i in place else (i, -2))
+        self.bwd_sched = [(i, place[i][1] if i in place else 0) for i in order]
+
+    def _place_mega(self, side):
+        """Chip-wide launches: the SSDN_OP_WGRAD records of a launch group consecutive (the executor runs such a run as ONE k_wgrad_mega
+        launch), behind the main-lane op that produces the group's last gradient operand -- or later, behind the data gradient of
+        the layer the group names (SPLIT_AFTER) --, directly followed by the group's slab reductions (a run of reductions is two launches).
+        A group that would fall inside a run of chainable main-lane ops waits behind the run."""
+        bwd = self.bwd
+        gof = {i: self.wgrad_group_of(bwd[i].a["layer"], self.is_skip_half(bwd[i])) for i in side}
+        at = {gof[i]: i for i in side if bwd[i].type == "wgrad"}           # (the last one of each group)
+        for g in at:
+            after = self._group_info[g][2]
+            dgrads = [i for i, op in enumerate(bwd) if op.type == "conv" and op.a["role"] == "dgrad" and op.a["layer"] == after]
+            if dgrads:
+                at[g] = max(at[g], dgrads[0])
+        _behind_runs(at, chain_runs(bwd))
+        return {i: ((at[gof[i]], gof[i], bwd[i].type == "wreduce", i), self._group_info[gof[i]][1]) for i in side}
+
+    def _place_layers(self, side):
+        """Per-layer launches, gradient bucket by gradient bucket (bucket_layers(split_head=False): head+dec1 | dec2..dec5 | encoder):
+        * every slab reduction at the end of its bucket: the executor merges a run of consecutive SSDN_OP_WREDUCE ops into two
+          launches, instead of two launches per layer (51 latency-bound launches, 0.52 ms per step in situ);
+        * the weight-gradient GEMMs of a bucket's layers at 16x16 pixels and below together, where the last of them stood: the executor
+          runs a run of consecutive small SSDN_OP_WGRAD ops as ONE launch (k_wgrad_multi; csrc/wgrad_mfma.hip::wgrad_mergeable);
+        * MAIN_LANE_WGRADS on the main lane, in front of their bucket's reductions;
+        * side records that would fall inside a run of chainable main-lane ops behind the run (CHAIN_POSTPONES);
+        * SSDN_OP_GRAD_PACK and the narrow net_out layer's data gradient behind it are ONE launch when adjacent (csrc/gradpack_dgrad.hip):
+          the weight-gradient record between them waits behind the pair (it needs the pair's output anyway);
+        * every other weight gradient where the planner put it."""
+        bwd = self.bwd
+        bucket_of = {name: k for k, b in enumerate(bucket_layers(self.layers, split_head=False)) for name in b}
+        kof = {i: bucket_of[bwd[i].a["layer"]] for i in side}
+        small = [i for i in side if bwd[i].type == "wgrad" and bwd[i].a["N"] * bwd[i].a["H"] * bwd[i].a["W"] <= WGRAD_SMALL_PX]
+        # (one merged launch per gradient bucket, so that a bucket still completes where it did; a single small layer stays put)
+        flush_at = {kof[i]: i for i in small if sum(1 for j in small if kof[j] == kof[i]) > 1}
+        grouped = {i for i in small if kof[i] in flush_at}
+        last = {}                                                           # bucket -> where its reductions go
+        for i in side:
+            last[kof[i]] = max(last.get(kof[i], -1), flush_at[kof[i]] if i in grouped else i)
+        runs = chain_runs(bwd)
+        _behind_runs(flush_at, runs, CHAIN_POSTPONES)
+        _behind_runs(last, runs, CHAIN_POSTPONES)
+        hold_to = -1
+        if bwd and bwd[0].type == "grad_pack":
+            j = next((k for k in range(1, len(bwd)) if bwd[k].type not in SIDE_OPS), -1)
+            if j > 1 and bwd[j].type == "conv" and bwd[j].a["role"] == "dgrad" and len(bwd[j].a["taps"]) == 1 and bwd[j].a["Ktot"] == 16:
+                hold_to = j
+        place = {}
+        for i in side:
+            k = kof[i]
+            # a bucket's merged small launch (0), its main-lane weight gradients (1), its reductions (2)
+            rank = lambda phase: ((k, 0) if SPLIT_SMALL_RUNS else (int(phase > 0), k)) + (phase, i)   # noqa: E731
+            if bwd[i].type == "wreduce":
+                place[i] = ((last[k],) + rank(2), WGRAD_LANE)
+            elif bwd[i].a["layer"] in MAIN_LANE_WGRADS:
+                place[i] = ((last[k],) + rank(1), 0)
+            elif i in grouped:
+                place[i] = ((flush_at[k],) + rank(0), WGRAD_LANE)
+            else:
+                place[i] = ((max(i, hold_to), -1, i), WGRAD_LANE)
+        return place

@@ -1,10 +1,11 @@
-"""CPU test of the backward list the engine emits (ssdn/hip/engine.py::DeviceNet._group_reductions): the planner's list re-ordered for the
+"""CPU test of the backward list the engine emits (ssdn/hip/graph.py::NetPlan.bwd_sched): the planner's data-flow list re-ordered for the
 merged launches (slab reductions per gradient bucket, small-layer weight gradients per bucket, chained main-lane runs, main-lane weight
 gradients).  Legal re-orderings only DELAY side-lane work; these are the invariants the executor's lane semantics rely on."""
 import pytest
 
 from ssdn.hip import engine as E
 from ssdn.hip.dp import bucket_layers
+from ssdn.hip import graph as G
 from ssdn.hip.graph import NetPlan
 
 
@@ -12,7 +13,8 @@ from ssdn.hip.graph import NetPlan
 def test_backward_list_order_invariants(cin, cout, bs, B, P):
     plan = NetPlan("m/", cin, cout, bs, B, P, P, cus=256)
     recs = [(op.type, i) for i, op in enumerate(plan.bwd)]               # the "argument struct" of record i is its planner index
-    out, names = E.DeviceNet._group_reductions(plan, recs)
+    out = [(plan.bwd[i].type, i, lane) for i, lane in plan.bwd_sched]
+    names = [plan.bwd[i].a["layer"] if plan.bwd[i].type == "wreduce" else None for i, _ in plan.bwd_sched]   # (the engine's: checked below)
     assert len(out) == len(recs) == len(names)
     pos = {r[1]: k for k, r in enumerate(out)}
     assert sorted(pos) == list(range(len(recs))), "the emitted list is a permutation of the planner's"
@@ -56,7 +58,7 @@ def test_backward_list_order_invariants(cin, cout, bs, B, P):
             assert ks == list(range(ks[0], ks[0] + len(ks)))
     # 5. weight gradients sent to the main lane come after the last data-gradient launch of their bucket, in front of its reductions
     for i, op in enumerate(plan.bwd):
-        if op.type == "wgrad" and op.a["layer"] in E.MAIN_LANE_WGRADS:
+        if op.type == "wgrad" and op.a["layer"] in G.MAIN_LANE_WGRADS:
             assert out[pos[i]][2] == 0
             assert all(pos[j] < pos[i] for j in mains if j < max(k for k, o in enumerate(plan.bwd) if o.type == "wgrad" and o.a["layer"] == op.a["layer"]))
     # 6. the chainable main-lane ops of the encoder end form one run without side-lane records in between
@@ -82,6 +84,7 @@ def test_bucket_marks_cover_every_lane_that_reduced_the_bucket(cin, cout, bs, B,
     plan = NetPlan("m/", cin, cout, bs, B, P, P, cus=256)
     flat = torch.zeros(plan.nparams)
     dn = E.DeviceNet(plan, torch.device("cpu"), flat, torch.zeros_like(flat))
+    assert dn._bwd_layers == [plan.bwd[i].a["layer"] if plan.bwd[i].type == "wreduce" else None for i, _ in plan.bwd_sched]
     buckets = bucket_layers(plan.layers)
     waits = {}
 

@@ -4,7 +4,6 @@ import pytest
 import torch
 
 import restate as R
-from ssdn.hip.engine import DeviceNet
 from ssdn.hip.graph import NetPlan, TAPS_BLIND, TAPS_PLAIN, View
 
 
@@ -73,14 +72,12 @@ def test_plan_input_grad_op(C, bs, B, P):
     assert [(op.type, op.a) for op in on.fwd] == [(op.type, op.a) for op in off.fwd]
     assert [(op.type, op.a) for op in on.pack] == [(op.type, op.a) for op in off.pack]
     assert {k: v for k, v in on.tensors.items() if k != "n/dx32"} == off.tensors
-    # the engine's list orderings (chip-wide / per-layer weight-gradient launches) keep it in place, on the main lane
-    recs = [(op.type, k) for k, op in enumerate(on.bwd)]
-    out, _ = DeviceNet._group_reductions(on, recs)
+    # the scheduled list (chip-wide / per-layer weight-gradient launches) keeps it in place, on the main lane
+    out = [(on.bwd[k].type, k, lane) for k, lane in on.bwd_sched]
     pos = [j for j, r in enumerate(out) if r[0] == "input_grad"]
-    assert len(pos) == 1 and len(out[pos[0]]) == 2            # (no lane of its own: OpList gives it lane 0)
+    assert len(pos) == 1 and out[pos[0]][2] == 0              # (the main lane)
     assert [r[1] for r in out].index(we[0]) < pos[0]
-    out_off, _ = DeviceNet._group_reductions(off, [(op.type, k) for k, op in enumerate(off.bwd)])
-    assert len(out) == len(out_off) + 1
+    assert len(out) == len(off.bwd_sched) + 1
 
 
 def test_input_grad_needs_a_training_plan():

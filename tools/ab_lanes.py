@@ -1,4 +1,4 @@
-"""Same-process A/B of an engine / planner constant on the bench workload (edit VARIANTS and the line that applies a variant: engine.MAIN_LANE_WGRADS, SPLIT_SMALL_RUNS, CHAIN_POSTPONES, DEFER_TAIL ... were all decided with this tool)."""
+"""Same-process A/B of an engine / planner constant on the bench workload (edit VARIANTS and the line that applies a variant: graph.MAIN_LANE_WGRADS, SPLIT_SMALL_RUNS, CHAIN_POSTPONES -- assigned before the Denoiser plans --, engine.DEFER_TAIL ... were all decided with this tool)."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "selfsupervised-denoising_amd"), ROOT]

@@ -28,7 +28,7 @@ for v, spec in VARIANTS.items():
     mode, lane = spec[0], spec[1]
     torch.manual_seed(0)
     G.WGRAD_MEGA = mode
-    E.MEGA_LANE = lane
+    G.MEGA_LANE = lane
     G.SPLIT_HEAD_CUS = spec[2] if len(spec) > 2 else (1, 2)
     G.SPLIT_GROUP0 = spec[3] if len(spec) > 3 else ("output_block",)
     d = Denoiser(B.make_cfg(), device=str(dev))

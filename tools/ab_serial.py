@@ -5,16 +5,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "selfsupervised-denoising_amd"), ROOT]
 import torch
 import bench as B
-from ssdn.hip import engine as E, graph as G
+from ssdn.hip import graph as G
 from ssdn.denoiser import Denoiser
 from ssdn.datasets import DevicePatchStream, NoisyDataset
 from ssdn.params import NoiseAlgorithm
 
 dev = torch.device("cuda", 0)
-VARIANTS = {"two_lanes_192": ({"wgrad": (1,), "wreduce": (1,)}, (3, 4)),
-            "serial_192": ({"wgrad": (0,), "wreduce": (0,)}, (3, 4)),
-            "serial_256": ({"wgrad": (0,), "wreduce": (0,)}, (1, 1)),
-            "two_lanes_256": ({"wgrad": (1,), "wreduce": (1,)}, (1, 1))}
+VARIANTS = {"two_lanes_192": (1, (3, 4)),        # (graph.WGRAD_LANE, graph.WGRAD_CU_FRAC)
+            "serial_192": (0, (3, 4)),
+            "serial_256": (0, (1, 1)),
+            "two_lanes_256": (1, (1, 1))}
 nd = NoisyDataset(None, "gauss25", NoiseAlgorithm.SELFSUPERVISED_DENOISING, pad_uniform=False, pad_multiple=32, square=True, training_mode=True)
 g = torch.Generator().manual_seed(1)
 u8 = [torch.randint(0, 256, (32, 3, 64, 64), generator=g, dtype=torch.uint8).pin_memory() for _ in range(4)]
@@ -22,9 +22,9 @@ idx = torch.arange(32)
 runs = {}
 for v, (lane, frac) in VARIANTS.items():
     torch.manual_seed(0)
-    E.OpList.LANE = lane
+    G.WGRAD_LANE = lane
     G.WGRAD_CU_FRAC = frac
-    E.MAIN_LANE_WGRADS = () if lane["wgrad"] == (0,) else ("encode_block_1.0", "encode_block_1.2")
+    G.MAIN_LANE_WGRADS = () if lane == 0 else ("encode_block_1.0", "encode_block_1.2")
     d = Denoiser(B.make_cfg(), device=str(dev))
     d.train()
     stream = DevicePatchStream(None, nd, dev, seed=1).attach(d)
