@@ -342,7 +342,7 @@ typedef struct ssdn_grad_pack_args {
  *   per-channel closed forms, g_net_out [B,2*C,H,W]; with C = 1 both are the same model (bit for bit).
  *   C must be 1 or 3.
  * style 2, IMPULSE (a new VALUE of `style`, no layout change: the ABI version stays; csrc/head_impulse.hip): with
- *   probability alpha a pixel was replaced, in all channels, by a colour uniform on [0,1)^C.  alpha: known: clamp(noise_param[b], 1e-3,
+ *   probability alpha a pixel was replaced, in all channels, by a colour uniform on (0,1]^C.  alpha: known: clamp(noise_param[b], 1e-3,
  *   0.999); const / var: min(softplus(est_raw - 4) + 1e-3, 0.999), no gradient through an active clamp.  With e = mu_x - 1/2:
  *     mu_y = alpha/2 + (1 - alpha) mu_x,  Sigma_y = (1 - alpha) Sigma_x + alpha/12 I + alpha (1 - alpha) e e^T   (the mixture's moments)
  *     l = 1/2 log det Sigma_y + 1/2 (y - mu_y)^T Sigma_y^-1 (y - mu_y)   (C = 1: log sy + d^2 / sy);  l -= 0.1 alpha for mode != known
@@ -524,7 +524,7 @@ typedef struct ssdn_event_args {
  *                                                      unbatched CHW sample, i.e. per channel: noise.py:34-39,55-56)
  *     gauss:    noisy = clean + param * N(0,1)                       (param = std dev as a fraction of 1)
  *     poisson:  noisy = (clean * param + Poisson(1)) / param         (RATE-1 noise on lambda x: the reference's quirk, noise.py:101-104)
- *     impulse:  noisy = Bernoulli(param) per PIXEL ? U[0,1)^C : clean   (style 2: one decision for all channels of a pixel, the untouched
+ *     impulse:  noisy = Bernoulli(param) per PIXEL ? U(0,1]^C : clean   (style 2: one decision for all channels of a pixel, the untouched
  *               pixel stays exactly u8 / 255; param = alpha in [0, 1], ONE draw per sample for a range, written to all C entries of
  *               param[b*C + c]; C <= 3; clip has nothing to do; the decision and the colours are a pure function of (seed, offset,
  *               stream, pixel), so the Noise2Void copy and ref32 work as for the other styles)
@@ -535,8 +535,10 @@ typedef struct ssdn_event_args {
  * [min(c - r, 0), min(c + r, size - 1)) without c itself, per axis (the reference's window: [0, c + r) in the interior, negative
  * indexes wrap like Python's); coords[b][i * (H / box) + j] = (c0, c1) as the reference returns them (image[:, c1, c0] is the
  * replaced pixel).  Random numbers: Philox4x32-10 keyed by `seed`, counter = (element, stream, offset): stateless, every launch
- * must pass a fresh `offset`.  The distributions are the reference's; the random STREAM is not torch's (parity of the noise is
- * statistical by construction). */
+ * must pass a fresh `offset`.  The distributions are the reference's; the random STREAM is not torch's (parity of the noise with the
+ * reference package is statistical by construction; the stream itself is pinned, element by element, against the
+ * host model tests/philox_ref.py).  The uniform values behind every draw lie in (0, 1]: 24 bits of a word, centred, and the top one
+ * rounds up to 1.0 in fp32. */
 typedef struct ssdn_noise_args {
     const void* clean_u8; /* [B,C,H,W] uint8 */
     float* clean32;       /* out [B,C,H,W] or NULL */

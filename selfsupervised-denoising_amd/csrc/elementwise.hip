@@ -892,7 +892,7 @@ static __device__ __forceinline__ bool n2v_select(const ssdn_noise_args& a, int 
     }
     return blind;
 }
-// IMPULSE (style 2): with probability alpha a pixel is replaced, in ALL channels, by a colour uniform on [0,1)^C; otherwise it stays exactly
+// IMPULSE (style 2): with probability alpha a pixel is replaced, in ALL channels, by a colour uniform on (0,1]^C; otherwise it stays exactly
 // u8 / 255 (clip has nothing to do).  One Philox draw per (pixel, realisation): word 0 decides, words 1..3 are the colour -- a pure function
 // of (seed, offset, stream, pixel), so the Noise2Void copy re-derives its neighbour's value like k_noise.  A ranged alpha is ONE draw per
 // sample (the mask is per pixel), written to all C entries of param.  A kernel of its own, for the same reason.

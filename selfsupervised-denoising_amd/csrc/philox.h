@@ -1,5 +1,5 @@
 // philox.h -- the library's counter-based random numbers, shared by the training patch stream (elementwise.hip: SSDN_OP_NOISE) and the
-// posterior sampler (head_posterior.hip: SSDN_OP_HEAD_POSTERIOR): Philox4x32-10, the map of 32 random bits to (0, 1) and the Box-Muller
+// posterior sampler (head_posterior.hip: SSDN_OP_HEAD_POSTERIOR): Philox4x32-10, the map of 32 random bits to (0, 1] and the Box-Muller
 // normal.  A value is a pure function of (key, counter); the callers lay the counter out as (element, stream, offset lo, offset hi) and key
 // it by the seed.  Streams: 0..4 are SSDN_OP_NOISE's (NS_* in elementwise.hip); PH_STREAM_POSTERIOR and above are the posterior sampler's.
 #pragma once
@@ -18,7 +18,7 @@ static __device__ __forceinline__ Ph4 philox4x32_10(unsigned c0, unsigned c1, un
     o.v[0] = c0; o.v[1] = c1; o.v[2] = c2; o.v[3] = c3;
     return o;
 }
-static __device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * (1.f / 16777216.f) + (0.5f / 16777216.f); }   // (0, 1)
+static __device__ __forceinline__ float u01(unsigned x) { return (float)(x >> 8) * (1.f / 16777216.f) + (0.5f / 16777216.f); }   // (0, 1]: the top 256 words round up to 1.0
 // one N(0,1) value from two random words (Box-Muller, the cosine branch)
 static __device__ __forceinline__ float ph_normal(unsigned a, unsigned b) {
     return sqrtf(-2.f * __logf(u01(a))) * __cosf(6.28318530718f * u01(b));

@@ -149,9 +149,10 @@ def op_inputs(style, mode, C, diag=0, B=2, H=5, W=7, alpha=0.5, seed=0):
 
 
 def fp32_yardstick(net_out, noisy, npar, style, mode, est_raw, diag, m64):
-    """the mirror in fp32 torch against float64, max abs error per output: what the number format alone costs on these inputs"""
+    """the mirror in fp32 torch against float64, max abs error per output (impulse: of the weight `w` too): what the number format alone
+    costs on these inputs"""
     m32 = posterior_ref(net_out, noisy, npar, style, mode, est_raw, diag, dtype=torch.float32)
-    fig = {k: float((m32[k].double() - m64[k]).abs().max()) for k in ("mean", "cov", "std")}
+    fig = {k: float((m32[k].double() - m64[k]).abs().max()) for k in ("mean", "cov", "std") + (("w",) if "w" in m64 else ())}
     print("fp32 mirror vs float64, max abs error: " + ", ".join("%s %.2e (max |.| %.2e)" % (k, v, float(m64[k].abs().max())) for k, v in fig.items()))
     return fig
 

@@ -1,10 +1,12 @@
 """SSDN_OP_NOISE (csrc/elementwise.hip::k_noise) -- the training patch stream's per-sample work on the device (SURVEY.md section 8f
 N2; reference: datasets/noise_wrapper.py:66-135, utils/noise.py:54-107, utils/n2v_ups.py:40-88).
 
-The random stream is the kernel's own (Philox), so parity with the reference is STATISTICAL (SURVEY.md section 8c "parity
+The random stream is the kernel's own (Philox), so parity with the REFERENCE PACKAGE is statistical (SURVEY.md section 8c "parity
 unpinned"): the moments of every noise style are compared with the values the LIVE reference produced on a constant 0.5 image
 (tests/golden/g_ckpt_contract.json "data_layer"/"styles", written by oracle/gen_golden.py), the Noise2Void geometry with
-"data_layer"/"n2v", and everything deterministic (clean / 255, clipping, parameter ranges, the replacement rule) exactly."""
+"data_layer"/"n2v", and everything deterministic (clean / 255, clipping, parameter ranges, the replacement rule) exactly.  The stream
+itself is pinned EXACTLY elsewhere: tests/test_hip_random_streams.py compares every element, count, hit, colour, coordinate and copied
+neighbour with the host model tests/philox_ref.py; the tests here remain the tie to the reference's styles."""
 import ctypes as C
 import json
 import os
