@@ -72,7 +72,8 @@ enum ssdn_op_type {
     SSDN_OP_HEAD_VJP = 23,     /* vector-Jacobian product of the SSDN head: any upstream gradient of LOSS / posterior mean / mu */
     SSDN_OP_MSE_VJP = 24,      /* the same for the (masked) MSE pipelines: LOSS / network output */
     SSDN_OP_ACCUM = 25,        /* dst[i] = fl(dst[i] + src[i]): folds a per-pass staging value into a running gradient sum */
-    SSDN_OP_HEAD_POSTERIOR = 26 /* per-pixel posterior of the SSDN head beyond its mean: covariance, std maps, samples (no planned list holds it) */
+    SSDN_OP_HEAD_POSTERIOR = 26, /* per-pixel posterior of the SSDN head beyond its mean: covariance, std maps, samples (no planned list holds it) */
+    SSDN_OP_SSIM = 27           /* per-sample SSIM of two image batches over each sample's un-padded extent, optional SSIM map (no planned list holds it) */
 };
 
 /* One record of the op list.  `args` points at the matching ssdn_*_args struct (host memory).
@@ -584,6 +585,42 @@ typedef struct ssdn_head_posterior_args {
     int32_t n_samples;    /* >= 1 when samples is given */
     uint64_t seed, offset;
 } ssdn_head_posterior_args;
+
+/* ---- SSDN_OP_SSIM ------------------------------------------------------------------------------
+ * The structural similarity index of Wang, Bovik, Sheikh and Simoncelli (2004) with the parameters of the authors' code: the window
+ * g[k] ~ exp(-(k - 5)^2 / (2 * 1.5^2)), k = 0..10, normalised to sum 1, applied separably as an 11 x 11 window at the positions where the
+ * whole window lies inside the image (no padding: an h x w image has (h - 10) x (w - 10) positions).  Per channel and position, E[.] the
+ * window-weighted sum:  mx = E[x], my = E[ref], sxx = E[x^2] - mx^2, syy = E[ref^2] - my^2, sxy = E[x ref] - mx my,
+ *     SSIM = (2 mx my + C1)(2 sxy + C2) / ((mx^2 + my^2 + C1)(sxx + syy + C2)),   C1 = 0.01^2, C2 = 0.03^2 (data range 1; nothing is clipped)
+ * ssim[b] = the plain mean over the channels and the positions of sample b's image, which is its un-padded extent ext[b] = (e1, e2) of
+ * the two spatial axes (SSDN_OP_METRICS' convention; NULL: the whole image).  ext is device memory: the kernel clamps it to [0,H] x [0,W].
+ * A sample whose extent is below 11 in either axis has no position: ssim[b] = NaN and nothing of its map is written.
+ * map (optional): the value of the window over rows i..i+10, columns j..j+10 goes to its centre, map[b,c,i+5,j+5]; every other element
+ * is left untouched.
+ * Arithmetic (csrc/ssim.hip): fp32 in; the five window sums, the formula and the mean in fp64 (the products of
+ * fp32 values are exact there, so E[x^2] - mx^2 does not cancel in the working precision); one rounding to fp32 per stored value.  One
+ * workgroup per (SSDN_SSIM_TILE_H x SSDN_SSIM_TILE_W tile of positions, channel, sample), tiles counted from (0,0) of the extent; each
+ * adds its positions in a fixed order into scratch, and a second launch adds a sample's tile sums in a fixed order that depends on the
+ * extent alone: ssim[b] does not depend on the padding around the extent, on map being requested or on the launch being repeated.
+ * scratch: device memory of SSDN_SSIM_SCRATCH_BYTES(B, C, H, W) bytes, 8-byte aligned, contents irrelevant before and after.
+ * Argument errors are raised before any device call (text prefixed "ssim:"): x, ref, ssim or scratch NULL, B or C < 1, H or W < 11,
+ * scratch_bytes below the rule, B * C or the tile rows above 65535.  Adding this op changed no existing struct: the ABI version stays. */
+#define SSDN_SSIM_WIN 11
+#define SSDN_SSIM_TILE_H 16
+#define SSDN_SSIM_TILE_W 32
+#define SSDN_SSIM_TILES(n, t) (((n) - (SSDN_SSIM_WIN - 1) + (t) - 1) / (t))
+#define SSDN_SSIM_SCRATCH_BYTES(B, C, H, W) \
+    ((int64_t)8 * (B) * (C) * SSDN_SSIM_TILES(H, SSDN_SSIM_TILE_H) * SSDN_SSIM_TILES(W, SSDN_SSIM_TILE_W))
+typedef struct ssdn_ssim_args {
+    const float* x;       /* [B,C,H,W] */
+    const float* ref;     /* [B,C,H,W] */
+    const int32_t* ext;   /* [B][2] or NULL */
+    int32_t B, C, H, W;
+    float* ssim;          /* out [B] */
+    float* map;           /* out [B,C,H,W] or NULL */
+    void* scratch;        /* per-tile partial sums (fp64) */
+    int64_t scratch_bytes;
+} ssdn_ssim_args;
 
 /* ---- SSDN_OP_INPUT_GRAD --------------------------------------------------------------------
  * replaces: the data gradient autograd propagates into the network input through the first conv (noise_network.py:69-71) and the

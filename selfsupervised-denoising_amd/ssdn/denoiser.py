@@ -467,16 +467,10 @@ class Denoiser(nn.Module):
             accs[kind] = torch.zeros(16, dtype=torch.float32, device=self.device)
         return accs[kind]
 
-    def accumulate_metrics(self, data: List, kind: str = "train", with_loss: bool = True, per_sample: bool = False):
-        """Add the metrics of the LAST `run_pipeline` / `train_step` batch (`data` = its inputs) to the device-resident accumulator
-        `kind` with one kernel launch (SSDN_OP_METRICS: loss, PSNR of IMG_DENOISED and IMG_MU against the clean image over each
-        sample's un-padded extent, noise / model std-dev x 255 -- what the reference trainer accumulates with ~20 ATen launches per
-        step, train.py:205-218, utils/data.py:94-105).  Nothing is copied to the host; `read_metrics` does that when the trainer
-        prints.  per_sample=True returns {"psnr_out": [B], "psnr_mu_out": [B]} of this batch (host tensors: synchronises)."""
-        eng = self._last_engine
-        if eng is None:
-            raise RuntimeError("accumulate_metrics() needs a preceding run_pipeline()")
-        meta = data[NoisyDataset.METADATA]
+    def _clean_and_extent(self, meta: Dict):
+        """The clean batch of a pipeline's metadata as the device kernels read it, and the un-padded extents of its samples:
+        -> (clean: contiguous fp32 [B,C,H,W] on the device; ext: int32 [B,2] on the device, or None when no sample is padded;
+        the extents on the host, int32 [B,2], or None without Metadata.IMAGE_SHAPE)."""
         MD = NoisyDataset.Metadata
         clean = meta[MD.CLEAN]
         B = clean.shape[0]
@@ -488,6 +482,18 @@ class Denoiser(nn.Module):
             shp = torch.as_tensor(shp).reshape(B, -1)[:, -2:].to(torch.int32)
             if bool((shp != torch.tensor(list(clean.shape[-2:]), dtype=torch.int32)).any()):
                 ext = shp.to(self.device, non_blocking=True).contiguous()
+        return clean, ext, shp
+
+    def accumulate_metrics(self, data: List, kind: str = "train", with_loss: bool = True, per_sample: bool = False):
+        """Add the metrics of the LAST `run_pipeline` / `train_step` batch (`data` = its inputs) to the device-resident accumulator
+        `kind` with one kernel launch (SSDN_OP_METRICS: loss, PSNR of IMG_DENOISED and IMG_MU against the clean image over each
+        sample's un-padded extent, noise / model std-dev x 255 -- what the reference trainer accumulates with ~20 ATen launches per
+        step, train.py:205-218, utils/data.py:94-105).  Nothing is copied to the host; `read_metrics` does that when the trainer
+        prints.  per_sample=True returns {"psnr_out": [B], "psnr_mu_out": [B]} of this batch (host tensors: synchronises)."""
+        eng = self._last_engine
+        if eng is None:
+            raise RuntimeError("accumulate_metrics() needs a preceding run_pipeline()")
+        clean, ext, _ = self._clean_and_extent(data[NoisyDataset.METADATA])
         eng.accumulate_metrics(self._metrics_acc(kind), clean, ext, with_loss=with_loss and self._has_loss_last)
         self._metrics_keep = (clean, ext)               # alive until the launch has run
         if per_sample:
@@ -499,6 +505,36 @@ class Denoiser(nn.Module):
                 res["psnr_mu_out"] = per[:, 2].clone()
             return res
         return None
+
+    def ssim(self, data: List, maps: bool = False) -> Dict[str, Tensor]:
+        """SSIM against the clean image for the LAST `run_pipeline` / `train_step` batch (`data` = its inputs), per sample over its
+        un-padded extent (ssdn.utils.calculate_ssim is the definition).  -> host float32 [B] tensors "ssim_nsy" (the noisy input),
+        "ssim_out" (IMG_DENOISED) and, for the SSDN pipeline, "ssim_mu_out" (IMG_MU); maps=True adds "map_nsy", "map_out"
+        ("map_mu_out"): [B,C,H,W], the value of every 11 x 11 window at its centre, zero where none is centred.  On a GPU the engine's
+        own buffers go through SSDN_OP_SSIM (csrc/ssim.hip: fp64 window sums, one rounding); a Denoiser on another device has no
+        engine and no last batch.  Reads only: outputs, metric accumulators, weights and plans stay what they were.  Synchronises."""
+        eng = self._last_engine
+        if eng is None:
+            raise RuntimeError("ssim() needs a preceding run_pipeline()")
+        meta = data[NoisyDataset.METADATA] if len(data) > NoisyDataset.METADATA else None
+        if not isinstance(meta, dict) or not torch.is_tensor(meta.get(NoisyDataset.Metadata.CLEAN)):
+            raise ValueError("ssim(): the batch has no clean image (Metadata.CLEAN)")
+        clean, ext, shp = self._clean_and_extent(meta)
+        if tuple(clean.shape) != (eng.B, eng.C, eng.H, eng.W):
+            raise ValueError("ssim(): the clean batch %s is not the last run's shape" % (tuple(clean.shape),))
+        small = min(clean.shape[-2:]) if shp is None else int(shp.min())
+        if small < 11:
+            raise ValueError("ssim(): an image extent of %d is below the 11 x 11 window" % small)
+        srcs = [("nsy", eng.inp), ("out", eng.pme if self._pipeline == Pipeline.SSDN else eng.main.tensor("out32"))]
+        if self._pipeline == Pipeline.SSDN:
+            srcs.append(("mu_out", eng.mu))
+        res = {}
+        for name, x in srcs:
+            val, smap = eng.ssim(x, clean, ext, want_map=maps)
+            res["ssim_" + name] = val.cpu()                      # (synchronises: the launch has run, the buffers are free for the next)
+            if maps:
+                res["map_" + name] = smap.cpu()
+        return res
 
     def reset_device_metrics(self, kind: str = "train"):
         """forget what `accumulate_metrics` has summed on the device since the last read (the trainer's reset_metrics)"""

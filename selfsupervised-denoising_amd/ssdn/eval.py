@@ -1,6 +1,6 @@
 """`DenoiserEvaluator` -- evaluation driver (drop-in for /root/reference/ssdn/ssdn/eval.py:18-125): load a `.wt` or `.training`
 file, pad every test image by reflection to a x32 multiple / square / uniform size (Kodak 768x768, BSD300 512x512), run the
-forward kernels, un-pad, per-image PSNR -> `psnrs.csv`, images -> `eval_imgs/`.  Reference defect fixed: `runs_dir` is honoured
+forward kernels, un-pad, per-image PSNR -> `psnrs.csv` (with `ssim` set: per-image SSIM -> `ssims.csv`), images -> `eval_imgs/`.  Reference defect fixed: `runs_dir` is honoured
 (eval.py:32-35 drops it)."""
 import logging
 import os
@@ -13,7 +13,7 @@ from ssdn.cfg import DEFAULT_RUN_DIR
 from ssdn.datasets import NoisyDataset
 from ssdn.denoiser import Denoiser
 from ssdn.params import PipelineOutput
-from ssdn.train import DenoiserTrainer
+from ssdn.train import _SSIM_CACHE, DenoiserTrainer
 
 logger = logging.getLogger("ssdn.eval")
 
@@ -74,6 +74,14 @@ class DenoiserEvaluator(DenoiserTrainer):
                 values += [self.calculate_psnr(outputs, key, unpad=True).cpu() for key in self.img_outputs(prefix="psnr")]
                 for i in range(n):
                     f.write(",".join(["{:04d}".format(output_0_index + i)] + ["{:.4f}".format(float(v[i])) for v in values]) + "\n")
+            per = outputs.get(_SSIM_CACHE)
+            if per is not None:                 # `ssdn eval --ssim`: the same rows, SSIM instead of PSNR
+                names = ["ssim_nsy"] + list(self.img_outputs(prefix="ssim").values())
+                with open(os.path.join(self.run_dir_path, "ssims.csv"), "a") as f:
+                    if output_0_index == 0:
+                        f.write(",".join(["id"] + names) + "\n")
+                    for i in range(n):
+                        f.write(",".join(["{:04d}".format(output_0_index + i)] + ["{:.6f}".format(float(per[k][i])) for k in names]) + "\n")
         return callback
 
     def save_posterior_outputs(self, outputs: Dict, output_0_index: int, batch_indexes) -> None:

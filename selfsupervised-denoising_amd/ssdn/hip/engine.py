@@ -369,6 +369,7 @@ class DenoiserEngine:
         self.g_fresh = self.loss_fwd = False
         self._vjp = None
         self._post = {}             # posterior(): cov / std / samples buffers, allocated on first use (no plan tensor)
+        self._ssim = {}             # ssim(): value / map / scratch buffers, allocated on first use (no plan tensor)
 
     # ---- op construction -----------------------------------------------------------------------------------
     def _gmax(self, net: Optional[DeviceNet]):
@@ -649,6 +650,31 @@ class DenoiserEngine:
                                 _ptr(buf["samples"]) if n_samples else None, n_samples, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1))
         OpList([("head_posterior", a)]).run(current_stream() if stream is None else stream)
         return {k: buf[k] for k, on in (("cov", cov), ("std", std), ("samples", n_samples > 0)) if on}
+
+    def ssim(self, x: torch.Tensor, clean: torch.Tensor, ext: Optional[torch.Tensor] = None, want_map: bool = False, stream=None):
+        """SSIM of `x` against `clean` (SSDN_OP_SSIM, csrc/ssim.hip) per sample over its un-padded extent: two launches on the engine's
+        stream behind the last forward.  x, clean: contiguous fp32 [B,C,H,W] device tensors of the engine's shape (x is normally one of
+        the engine's own: inp, pme, mu, the network output); ext: int32 [B,2] device tensor or None, accumulate_metrics' convention.
+        -> (ssim [B], map [B,C,H,W] or None): the engine's own buffers, allocated on first use outside the plan's tensors and
+        overwritten by the next call.  The map is zero where no window is centred."""
+        shape = (self.B, self.C, self.H, self.W)
+        for name, t in (("x", x), ("clean", clean)):
+            if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape or t.device != self.inp.device:
+                raise L.SsdnHipError("ssim: %s must be a contiguous fp32 [B,C,H,W] device tensor of the engine's shape" % name)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        buf = self._ssim
+        if "val" not in buf:
+            buf["val"] = torch.zeros((self.B,), **f32)
+            buf["scratch"] = torch.zeros((L.ssim_scratch_bytes(*shape) // 8,), dtype=torch.float64, device=self.device)
+        if want_map:
+            if "map" not in buf:
+                buf["map"] = torch.zeros(shape, **f32)
+            else:
+                buf["map"].zero_()
+        a = L.SsimArgs(_ptr(x), _ptr(clean), _ptr(ext) if ext is not None else None, *shape, _ptr(buf["val"]),
+                       _ptr(buf["map"]) if want_map else None, _ptr(buf["scratch"]), buf["scratch"].numel() * 8)
+        OpList([("ssim", a)]).run(current_stream() if stream is None else stream)
+        return buf["val"], (buf["map"] if want_map else None)
 
     def _head_addend(self, on: bool) -> None:
         """input_grad engines: whether the first network input gradient of the sum adds the head term the VJP left in `dx`"""

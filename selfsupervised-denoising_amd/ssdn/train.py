@@ -44,6 +44,7 @@ from ssdn.params import ConfigValue, DatasetType, HistoryValue, Pipeline, Pipeli
 from ssdn.utils import Metric, MetricDict, TrackedTime, separator
 
 logger = logging.getLogger("ssdn.train")
+_SSIM_CACHE = "_ssim_per_sample"          # ... and of the per-sample SSIM values of an evaluation with DenoiserTrainer.ssim set
 _PSNR_CACHE = "_psnr_per_sample"          # key of the per-sample PSNR values the device metric kernel produced for an output dict
 
 
@@ -104,6 +105,8 @@ class DenoiserTrainer:
         # minibatches per optimiser step (gradient accumulation).  Not a ConfigValue (that enum is a pickle contract with the reference):
         # K > 1 travels as the extra top-level key "accumulate" of a `.training` file
         self.accumulate = 1
+        # evaluation also reports SSIM (`ssdn eval --ssim`): ssim_out / ssim_mu_out next to the PSNRs.  A plain attribute, not a ConfigValue
+        self.ssim = False
 
     # ---- target -----------------------------------------------------------------------------------------------------------
     @property
@@ -276,6 +279,10 @@ class DenoiserTrainer:
                     outputs[_PSNR_CACHE] = {key: per[name] for key, name in self.img_outputs(prefix="psnr").items() if name in per}
                 for key, name in self.img_outputs(prefix="psnr").items():
                     eval_history[name] += self.calculate_psnr(outputs, key, unpad=True)
+                if self.ssim:
+                    outputs[_SSIM_CACHE] = per = self.calculate_ssim(data, outputs)
+                    for name in self.img_outputs(prefix="ssim").values():
+                        eval_history[name] += per[name]
                 if output_callback:
                     output_callback(idx, outputs)
                 idx += image_count
@@ -347,7 +354,8 @@ class DenoiserTrainer:
 
     @staticmethod
     def _metric_strs(md) -> list:
-        return ["{}={:8.2f}".format(k, float(torch.as_tensor(m.accumulated()).float().mean()))
+        # (an SSIM lives in [-1, 1]: four decimals where the other metrics print two)
+        return [("{}={:8.4f}" if str(k).startswith("ssim") else "{}={:8.2f}").format(k, float(torch.as_tensor(m.accumulated()).float().mean()))
                 for k, m in md.items() if isinstance(m, Metric) and not m.empty()]
 
     def train_state_str(self) -> str:
@@ -379,6 +387,18 @@ class DenoiserTrainer:
         if self.cfg[ConfigValue.PIPELINE] == Pipeline.SSDN:
             outs[PipelineOutput.IMG_MU] = "mu_out"
         return {k: ("_".join((prefix, v)) if prefix else v) for k, v in outs.items()}
+
+    def calculate_ssim(self, data, outputs: Dict) -> Dict[str, Tensor]:
+        """{"ssim_nsy", "ssim_out"[, "ssim_mu_out"]}: host float32 [B], each image against its clean image over its un-padded extent.
+        On a GPU one Denoiser.ssim call for the batch just run (SSDN_OP_SSIM); otherwise ssdn.utils.calculate_ssim on the un-padded pairs."""
+        if getattr(self.denoiser, "device", torch.device("cpu")).type == "cuda":
+            return self.denoiser.ssim(data)
+        metadata = data[NoisyDataset.METADATA]
+        clean = NoisyDataset.unpad(metadata[NoisyDataset.Metadata.CLEAN], metadata)
+        imgs = {"ssim_nsy": data[NoisyDataset.INPUT]}
+        imgs.update({name: outputs[key] for key, name in self.img_outputs(prefix="ssim").items()})
+        return {name: torch.stack([ssdn.utils.calculate_ssim(a.cpu(), b.cpu()) for a, b in zip(NoisyDataset.unpad(img, metadata), clean)])
+                for name, img in imgs.items()}
 
     @staticmethod
     def calculate_psnr(outputs: Dict, output: PipelineOutput, unpad: bool = True) -> Tensor:

@@ -39,6 +39,49 @@ def calculate_psnr(img: Tensor, ref: Tensor) -> Tensor:
     return mse2psnr(mse, img.is_floating_point())
 
 
+SSIM_WIN, SSIM_SIGMA, SSIM_C1, SSIM_C2 = 11, 1.5, 0.01 ** 2, 0.03 ** 2
+
+
+def ssim_window(device=None) -> Tensor:
+    """g[k] ~ exp(-(k - 5)^2 / (2 * 1.5^2)), k = 0..10, normalised to sum 1 (float64)"""
+    k = torch.arange(SSIM_WIN, dtype=torch.float64, device=device) - SSIM_WIN // 2
+    g = torch.exp(-(k * k) / (2 * SSIM_SIGMA ** 2))
+    return g / g.sum()
+
+
+def calculate_ssim(img: Tensor, ref: Tensor, full: bool = False):
+    """Per-sample SSIM for BCHW (or a single CHW image) -- the specification SSDN_OP_SSIM (csrc/ssim.hip) is held to, in float64.
+    Wang, Bovik, Sheikh, Simoncelli 2004 with the parameters of the authors' code (scikit-image: gaussian_weights=True,
+    use_sample_covariance=False, data_range=1): an 11 x 11 separable Gaussian window of sd 1.5 at the positions where it lies wholly
+    inside the image (no padding), C1 = 0.01^2, C2 = 0.03^2, the raw float images (nothing is clipped, as in calculate_psnr); the
+    value is the plain mean over channels and positions, NaN for an image below 11 pixels in either axis.  Returns float32 like
+    calculate_psnr ([B], or a scalar for CHW); full=True: (that, the float64 map [B, C, H - 10, W - 10] / [C, H - 10, W - 10])."""
+    import torch.nn.functional as F
+    single = img.dim() == 3
+    x = (img[None] if single else img).to(torch.float64)
+    y = (ref[None] if single else ref).to(torch.float64)
+    if x.dim() != 4 or x.shape != y.shape:
+        raise ValueError("calculate_ssim: two BCHW (or CHW) images of one shape, got %s and %s" % (tuple(img.shape), tuple(ref.shape)))
+    B, C, H, W = x.shape
+    if H < SSIM_WIN or W < SSIM_WIN:
+        val = torch.full((B,), float("nan"), dtype=torch.float32, device=x.device)
+        smap = torch.zeros((B, C, max(H - SSIM_WIN + 1, 0), max(W - SSIM_WIN + 1, 0)), dtype=torch.float64, device=x.device)
+    else:
+        g = ssim_window(x.device)
+
+        def win(t):                  # E[t]: 11 taps along the rows, then 11 down the columns, every plane on its own
+            t = t.reshape(B * C, 1, H, W)
+            t = F.conv2d(F.conv2d(t, g.view(1, 1, 1, -1)), g.view(1, 1, -1, 1))
+            return t.reshape(B, C, H - SSIM_WIN + 1, W - SSIM_WIN + 1)
+        mx, my = win(x), win(y)
+        sxx, syy, sxy = win(x * x) - mx * mx, win(y * y) - my * my, win(x * y) - mx * my
+        smap = ((2 * mx * my + SSIM_C1) * (2 * sxy + SSIM_C2)) / ((mx * mx + my * my + SSIM_C1) * (sxx + syy + SSIM_C2))
+        val = smap.reshape(B, -1).mean(1).to(torch.float32)
+    if single:
+        val, smap = val[0], smap[0]
+    return (val, smap) if full else val
+
+
 # ---- image I/O helpers of the trainer / evaluator (utils/data.py:69-125) ------------------------------------------------------
 def tensor2image(img: Tensor):
     """CHW float tensor in [0,1] -> PIL image.  The dataset classes hand out tensors with H and W SWAPPED (PIL data
