@@ -278,7 +278,10 @@ typedef struct ssdn_wgrad_args {
  * gw[m][cin][ky][kx] (fp32 OIHW, the checkpoint layout) = inv_scale * sum_s slab[s][t][m][k(cin)],
  * gb[m] = inv_scale * sum_s bslab[s][m];  k(cin) = cin (cin < c0) else c0 + (cin - c0) i.e. padding removed:
  * real input channels are [0,c0) and [c0, c0+c1_real).  inv_scale is read from device memory (loss-scale word).
- * Slabs are summed in a fixed order (groups of 32 in index order, then the groups in order): bit-reproducible.
+ * Slabs are summed in a fixed order, every sum a chain of fp32 adds that starts from 0.f: bit-reproducible.  Weights: groups of 32
+ * slabs in index order, then the group sums in order (nslabs <= 32: one chain over all slabs).  Bias: ONE chain over all slabs in
+ * index order, no groups (bslab is never used as scratch).  The sum is multiplied by inv_scale with one rounding.
+ * (tests/test_hip_optimiser.py holds the device to this order bit for bit.)
  * NOTE: the slab buffer is used as scratch (partial sums are written back into it).
  * accumulate = 1 (gradient accumulation over micro-batches): the epilogue ADDS instead of storing,
  *   gw[o] = fl(gw[o] + fl(inv_scale * sum)),  gb[m] = fl(gb[m] + fl(inv_scale * sum)):
