@@ -73,7 +73,8 @@ enum ssdn_op_type {
     SSDN_OP_MSE_VJP = 24,      /* the same for the (masked) MSE pipelines: LOSS / network output */
     SSDN_OP_ACCUM = 25,        /* dst[i] = fl(dst[i] + src[i]): folds a per-pass staging value into a running gradient sum */
     SSDN_OP_HEAD_POSTERIOR = 26, /* per-pixel posterior of the SSDN head beyond its mean: covariance, std maps, samples (no planned list holds it) */
-    SSDN_OP_SSIM = 27           /* per-sample SSIM of two image batches over each sample's un-padded extent, optional SSIM map (no planned list holds it) */
+    SSDN_OP_SSIM = 27,          /* per-sample SSIM of two image batches over each sample's un-padded extent, optional SSIM map (no planned list holds it) */
+    SSDN_OP_CALIBRATION = 28    /* per-sample calibration statistics of the posterior N(mean, cov) against the clean image, optional z histogram / z map (no planned list holds it) */
 };
 
 /* One record of the op list.  `args` points at the matching ssdn_*_args struct (host memory).
@@ -624,6 +625,52 @@ typedef struct ssdn_ssim_args {
     void* scratch;        /* per-tile partial sums (fp64) */
     int64_t scratch_bytes;
 } ssdn_ssim_args;
+
+/* ---- SSDN_OP_CALIBRATION -----------------------------------------------------------------------
+ * How well the per-pixel posterior N(mean, S) (SSDN_OP_HEAD_POSTERIOR's cov, upper triangle 00, 01, 02, 11, 12, 22; C = 1: the variance)
+ * describes the errors actually made against the clean image ref, per sample over its un-padded extent ext[b] = (e1, e2) (SSDN_OP_METRICS'
+ * convention; NULL: the whole image; device memory, clamped to [0,H] x [0,W] by the kernel).  ssdn.utils.calculate_calibration is the
+ * float64 specification.  Per pixel, everything in fp64 from the fp32 inputs, r = ref - mean, in this fixed order (C = 3):
+ *     p0 = s00, l00 = sqrt(p0), l10 = s01 / l00, l20 = s02 / l00;   p1 = s11 - l10^2, l11 = sqrt(p1), l21 = (s12 - l20 l10) / l11;
+ *     p2 = s22 - l20^2 - l21^2, l22 = sqrt(p2);   w0 = r0 / l00, w1 = (r1 - l10 w0) / l11, w2 = (r2 - l20 w0 - l21 w1) / l22;
+ *     d2 = w0^2 + w1^2 + w2^2, logdet = ln p0 + ln p1 + ln p2      (C = 1: p0 = s, d2 = r^2 / s, logdet = ln s);   z_c = r_c / sqrt(s_cc).
+ * A pixel is valid iff all of its inputs are finite, every pivot p_k > 0 and every s_cc > 0; otherwise it is degenerate: counted in
+ * stats[1] and left out of everything else.  stats[b][12], fp64:
+ *     0: N, the valid pixels   1: the degenerate pixels   2: sum d2   3: sum logdet   4: sum |r|^2 (over channels)   5: sum tr S
+ *     6, 7, 8: the (valid pixel, channel) pairs with |z_c| <= 1, 2, 3
+ *     9, 10, 11: the valid pixels with d2 <= the chi^2_C quantile at 0.5, 0.9, 0.99 (SSDN_CALIB_CHI2_C1 / _C3)
+ * hist (optional) [B][C][SSDN_CALIB_HIST_BINS]: counts of z_c over the valid pixels; bin 0: z < -4, bin 1 + floor(4 z + 16): -4 <= z < 4
+ * (32 bins of width 0.25), bin 33: z >= 4.  zmap (optional) [B,C,H,W]: z_c, rounded once to fp32, inside the extent only (NaN at its
+ * degenerate pixels); every other element is left untouched.  stats and hist of a sample with an empty extent are zeros; the op zeroes
+ * what it accumulates into.
+ * Arithmetic (csrc/calibration.hip): one pixel per thread, the pixels of a sample's extent numbered row-major
+ * n = i * e2 + j, SSDN_CALIB_BLOCK of them per workgroup; fp64 with contraction off, so every per-pixel value is the specification's.
+ * The four floating-point sums are added per workgroup in a fixed order into scratch and per sample by a second launch in an order that
+ * depends on the extent alone; the counts are integers (LDS, then scratch; the histogram through atomicAdd).  Sample b's outputs do not
+ * depend on the padding around its extent, on hist or zmap being requested, on the other samples or on the launch being repeated.
+ * scratch: device memory of SSDN_CALIB_SCRATCH_BYTES(B, C, H, W) bytes, 8-byte aligned, contents irrelevant before and after.
+ * Argument errors are raised before any device call (text prefixed "calibration:"): mean, cov, ref, stats or scratch NULL, C not 1 or 3,
+ * B, H or W < 1, scratch_bytes below the rule or scratch misaligned, B above 65535 or H * W above 2^31 - 1 - SSDN_CALIB_BLOCK.
+ * Adding this op changed no existing struct: the ABI version stays. */
+#define SSDN_CALIB_BLOCK 256
+#define SSDN_CALIB_NSTATS 12
+#define SSDN_CALIB_HIST_BINS 34
+#define SSDN_CALIB_CHI2_C1 { 0.45493642311957, 2.70554345409541, 6.63489660102120 }
+#define SSDN_CALIB_CHI2_C3 { 2.36597388437534, 6.25138863117032, 11.3448667301444 }
+#define SSDN_CALIB_SCRATCH_BYTES(B, C, H, W) \
+    ((int64_t)8 * SSDN_CALIB_NSTATS * (B) * (((int64_t)(H) * (W) + SSDN_CALIB_BLOCK - 1) / SSDN_CALIB_BLOCK))
+typedef struct ssdn_calibration_args {
+    const float* mean;    /* [B,C,H,W] */
+    const float* cov;     /* [B, C(C+1)/2, H, W] */
+    const float* ref;     /* [B,C,H,W] */
+    const int32_t* ext;   /* [B][2] or NULL */
+    int32_t B, C, H, W;
+    double* stats;                /* out [B][12] */
+    unsigned long long* hist;     /* out [B][C][34] or NULL */
+    float* zmap;                  /* out [B,C,H,W] or NULL */
+    void* scratch;                /* per-workgroup partial sums and counts (8 bytes each) */
+    int64_t scratch_bytes;
+} ssdn_calibration_args;
 
 /* ---- SSDN_OP_INPUT_GRAD --------------------------------------------------------------------
  * replaces: the data gradient autograd propagates into the network input through the first conv (noise_network.py:69-71) and the

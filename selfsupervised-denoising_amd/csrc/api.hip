@@ -111,6 +111,7 @@ int ssdn_struct_size(int op_type) {
         case SSDN_OP_ACCUM: return (int)sizeof(ssdn_accum_args);
         case SSDN_OP_HEAD_POSTERIOR: return (int)sizeof(ssdn_head_posterior_args);
         case SSDN_OP_SSIM: return (int)sizeof(ssdn_ssim_args);
+        case SSDN_OP_CALIBRATION: return (int)sizeof(ssdn_calibration_args);
         default: return -1;
     }
 }
@@ -382,6 +383,7 @@ int ssdn_run_ops(const ssdn_op* ops, int n, void* stream) {
             case SSDN_OP_ACCUM: rc = launch_accum((const ssdn_accum_args*)p, s); break;
             case SSDN_OP_HEAD_POSTERIOR: rc = launch_head_posterior((const ssdn_head_posterior_args*)p, s); break;
             case SSDN_OP_SSIM: rc = launch_ssim((const ssdn_ssim_args*)p, s); break;
+            case SSDN_OP_CALIBRATION: rc = launch_calibration((const ssdn_calibration_args*)p, s); break;
             case SSDN_OP_ZERO: {
                 const ssdn_zero_args* z = (const ssdn_zero_args*)p;
                 if (z->bytes & 15) return ssdn_set_error("op %d: zero size must be a multiple of 16", i);

@@ -536,6 +536,40 @@ class Denoiser(nn.Module):
                 res["map_" + name] = smap.cpu()
         return res
 
+    def calibration(self, data: List, hist: bool = False, maps: bool = False) -> Dict[str, Tensor]:
+        """Calibration of the per-pixel posterior N(IMG_DENOISED, cov) against the clean image for the LAST `run_pipeline` / `train_step`
+        batch (`data` = its inputs), per sample over its un-padded extent (ssdn.utils.calculate_calibration is the definition).  -> host
+        float64 [B] tensors "nll" (nats per pixel-channel), "maha" (mean squared Mahalanobis distance per channel: ideal 1, above 1 the
+        model is over-confident), "rmse_ratio" (actual over predicted RMSE), "cover_1s" / "cover_2s" / "cover_3s" (share of |z_c| <= 1, 2,
+        3; nominal 0.6827, 0.9545, 0.9973), "cover_50" / "cover_90" / "cover_99" (share of pixels inside the chi^2_C region of that
+        level), "degenerate" (share of pixels whose covariance is not positive definite or not finite: left out of the rest), and the raw
+        "stats" [B,12].  hist=True adds "hist", int64 [B,C,34] (z_c in 32 bins of width 0.25 over [-4, 4) and the two tails); maps=True
+        adds "zmap" [B,C,H,W], NaN at degenerate pixels and outside the extents.  For an impulse model the posterior is a two-component
+        mixture and cov its moment-matched covariance (see `posterior`): the values describe that Gaussian.  On a GPU one
+        SSDN_OP_HEAD_POSTERIOR and one SSDN_OP_CALIBRATION launch behind the last forward (csrc/calibration.hip: fp64 per pixel); a
+        Denoiser on another device has no engine and no last batch.  Reads only: outputs, metric accumulators, weights, plans and the
+        last engines stay what they were.  Synchronises.  SSDN pipeline only."""
+        if self._pipeline != Pipeline.SSDN:
+            raise NotImplementedError("Denoiser.calibration: the %s pipeline has no posterior covariance (SSDN pipeline only)" % self._pipeline.value)
+        eng = self._last_engine
+        if eng is None:
+            raise RuntimeError("calibration() needs a preceding run_pipeline()")
+        meta = data[NoisyDataset.METADATA] if len(data) > NoisyDataset.METADATA else None
+        if not isinstance(meta, dict) or not torch.is_tensor(meta.get(NoisyDataset.Metadata.CLEAN)):
+            raise ValueError("calibration(): the batch has no clean image (Metadata.CLEAN)")
+        clean, ext, _ = self._clean_and_extent(meta)
+        if tuple(clean.shape) != (eng.B, eng.C, eng.H, eng.W):
+            raise ValueError("calibration(): the clean batch %s is not the last run's shape" % (tuple(clean.shape),))
+        stats, dhist, dmap = eng.calibration(clean, ext, want_hist=hist, want_map=maps)
+        stats = stats.cpu()                                      # (synchronises: the launches have run, the buffers are free for the next)
+        res = dict(ssdn.utils.calibration_values(stats, eng.C))
+        res["stats"] = stats
+        if hist:
+            res["hist"] = dhist.cpu()
+        if maps:
+            res["zmap"] = dmap.cpu()
+        return res
+
     def reset_device_metrics(self, kind: str = "train"):
         """forget what `accumulate_metrics` has summed on the device since the last read (the trainer's reset_metrics)"""
         if kind in self.__dict__.get("_macc", {}):

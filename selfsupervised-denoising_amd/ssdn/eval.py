@@ -1,6 +1,7 @@
 """`DenoiserEvaluator` -- evaluation driver (drop-in for /root/reference/ssdn/ssdn/eval.py:18-125): load a `.wt` or `.training`
 file, pad every test image by reflection to a x32 multiple / square / uniform size (Kodak 768x768, BSD300 512x512), run the
-forward kernels, un-pad, per-image PSNR -> `psnrs.csv` (with `ssim` set: per-image SSIM -> `ssims.csv`), images -> `eval_imgs/`.  Reference defect fixed: `runs_dir` is honoured
+forward kernels, un-pad, per-image PSNR -> `psnrs.csv` (with `ssim` set: per-image SSIM -> `ssims.csv`; with `calibration` set:
+per-image posterior calibration -> `calibration.csv`, the z-score histogram of the whole evaluation -> `calibration_hist.csv`), images -> `eval_imgs/`.  Reference defect fixed: `runs_dir` is honoured
 (eval.py:32-35 drops it)."""
 import logging
 import os
@@ -13,7 +14,7 @@ from ssdn.cfg import DEFAULT_RUN_DIR
 from ssdn.datasets import NoisyDataset
 from ssdn.denoiser import Denoiser
 from ssdn.params import PipelineOutput
-from ssdn.train import _SSIM_CACHE, DenoiserTrainer
+from ssdn.train import _CALIB_CACHE, _SSIM_CACHE, DenoiserTrainer
 
 logger = logging.getLogger("ssdn.eval")
 
@@ -45,6 +46,8 @@ class DenoiserEvaluator(DenoiserTrainer):
         logger.info(ssdn.utils.separator())
         logger.info("EVALUATION STARTED")
         self._evaluate(self.testloader, self.evaluation_output_callback(self.testset))
+        if self.calibration and self.calibration_hist is not None:
+            self.save_calibration_hist()
         logger.info(self.eval_state_str("EVALUATION RESULT"))
         logger.info("EVALUATION FINISHED")
         logger.info(ssdn.utils.separator())
@@ -82,7 +85,31 @@ class DenoiserEvaluator(DenoiserTrainer):
                         f.write(",".join(["id"] + names) + "\n")
                     for i in range(n):
                         f.write(",".join(["{:04d}".format(output_0_index + i)] + ["{:.6f}".format(float(per[k][i])) for k in names]) + "\n")
+            cal = outputs.get(_CALIB_CACHE)
+            if cal is not None:                 # `ssdn eval --calibration`: the same rows, the calibration of the posterior covariance
+                names = list(ssdn.utils.data.CALIB_VALUES)
+                with open(os.path.join(self.run_dir_path, "calibration.csv"), "a") as f:
+                    if output_0_index == 0:
+                        f.write(",".join(["id"] + names) + "\n")
+                    for i in range(n):
+                        f.write(",".join(["{:04d}".format(output_0_index + i)] + ["{:.6f}".format(float(cal[k][i])) for k in names]) + "\n")
         return callback
+
+    def save_calibration_hist(self) -> None:
+        """`calibration_hist.csv`: the z-score histogram summed over the whole evaluation, one row per bin: bin_lo, bin_hi (the two end
+        bins reach to -inf / inf), expected = Phi(hi) - Phi(lo) of a standard normal, and per channel the fraction of its z-scores in
+        the bin (a calibrated model follows `expected`)."""
+        import math
+        hist = self.calibration_hist.to(torch.float64)
+        frac = hist / hist.sum(1, keepdim=True)
+        edges = [-math.inf] + [-4.0 + 0.25 * k for k in range(33)] + [math.inf]
+        phi = lambda x: 0.5 * (1.0 + math.erf(x / math.sqrt(2.0)))      # noqa: E731
+        with open(os.path.join(self.run_dir_path, "calibration_hist.csv"), "w") as f:
+            f.write(",".join(["bin_lo", "bin_hi", "expected"] + ["ch{}".format(c) for c in range(hist.shape[0])]) + "\n")
+            for k in range(hist.shape[1]):
+                lo, hi = edges[k], edges[k + 1]
+                f.write(",".join(["{:g}".format(lo), "{:g}".format(hi), "{:.8f}".format(phi(hi) - phi(lo))]
+                                 + ["{:.8f}".format(float(frac[c, k])) for c in range(hist.shape[0])]) + "\n")
 
     def save_posterior_outputs(self, outputs: Dict, output_0_index: int, batch_indexes) -> None:
         """`posterior/img_{index:05}_std.npy` (float32 [C,h,w], un-padded, upright) and `posterior/img_{index:05}_sample{k}.png` for the

@@ -370,6 +370,7 @@ class DenoiserEngine:
         self._vjp = None
         self._post = {}             # posterior(): cov / std / samples buffers, allocated on first use (no plan tensor)
         self._ssim = {}             # ssim(): value / map / scratch buffers, allocated on first use (no plan tensor)
+        self._calib = {}            # calibration(): stats / hist / zmap / scratch buffers, allocated on first use (no plan tensor)
 
     # ---- op construction -----------------------------------------------------------------------------------
     def _gmax(self, net: Optional[DeviceNet]):
@@ -675,6 +676,34 @@ class DenoiserEngine:
                        _ptr(buf["map"]) if want_map else None, _ptr(buf["scratch"]), buf["scratch"].numel() * 8)
         OpList([("ssim", a)]).run(current_stream() if stream is None else stream)
         return buf["val"], (buf["map"] if want_map else None)
+
+    def calibration(self, clean: torch.Tensor, ext: Optional[torch.Tensor] = None, want_hist: bool = False, want_map: bool = False, stream=None):
+        """Calibration statistics of the LAST forward's posterior N(pme, cov) against `clean` (SSDN_OP_CALIBRATION, csrc/calibration.hip)
+        per sample over its un-padded extent: one posterior(cov=True, std=False) launch behind that forward, then the calibration op on
+        self.pme, that cov buffer and clean.  clean: contiguous fp32 [B,C,H,W] device tensor of the engine's shape; ext: int32 [B,2] device
+        tensor or None, accumulate_metrics' convention.  -> (stats [B,12] float64, hist [B,C,34] int64 or None, zmap [B,C,H,W] or None): the
+        engine's own buffers, allocated on first use outside the plan's tensors and overwritten by the next call.  The map is NaN outside
+        the extents."""
+        shape = (self.B, self.C, self.H, self.W)
+        if clean.dtype != torch.float32 or not clean.is_contiguous() or tuple(clean.shape) != shape or clean.device != self.inp.device:
+            raise L.SsdnHipError("calibration: clean must be a contiguous fp32 [B,C,H,W] device tensor of the engine's shape")
+        s = current_stream() if stream is None else stream
+        cov = self.posterior(cov=True, std=False, stream=s)["cov"]
+        buf = self._calib
+        if "stats" not in buf:
+            buf["stats"] = torch.zeros((self.B, L.CALIB_NSTATS), dtype=torch.float64, device=self.device)
+            buf["scratch"] = torch.zeros((L.calib_scratch_bytes(*shape) // 8,), dtype=torch.float64, device=self.device)
+        if want_hist and "hist" not in buf:
+            buf["hist"] = torch.zeros((self.B, self.C, L.CALIB_HIST_BINS), dtype=torch.int64, device=self.device)
+        if want_map:
+            if "zmap" not in buf:
+                buf["zmap"] = torch.empty(shape, dtype=torch.float32, device=self.device)
+            buf["zmap"].fill_(float("nan"))
+        a = L.CalibrationArgs(_ptr(self.pme), _ptr(cov), _ptr(clean), _ptr(ext) if ext is not None else None, *shape, _ptr(buf["stats"]),
+                              _ptr(buf["hist"]) if want_hist else None, _ptr(buf["zmap"]) if want_map else None,
+                              _ptr(buf["scratch"]), buf["scratch"].numel() * 8)
+        OpList([("calibration", a)]).run(s)
+        return buf["stats"], (buf["hist"] if want_hist else None), (buf["zmap"] if want_map else None)
 
     def _head_addend(self, on: bool) -> None:
         """input_grad engines: whether the first network input gradient of the sum adds the head term the VJP left in `dx`"""

@@ -45,7 +45,10 @@ from ssdn.utils import Metric, MetricDict, TrackedTime, separator
 
 logger = logging.getLogger("ssdn.train")
 _SSIM_CACHE = "_ssim_per_sample"          # ... and of the per-sample SSIM values of an evaluation with DenoiserTrainer.ssim set
-_PSNR_CACHE = "_psnr_per_sample"          # key of the per-sample PSNR values the device metric kernel produced for an output dict
+_CALIB_CACHE = "_calibration_per_sample"  # ... and of the per-sample calibration values with DenoiserTrainer.calibration set
+_POSTERIOR_COV = "_posterior_cov"         # (an output dict may bring the posterior covariance [B, C(C+1)/2, H, W] along: the path without a GPU)
+CALIB_METRICS = ("nll", "maha", "rmse_ratio", "cover_2s")     # what an evaluation reports as calib_<name>
+_PSNR_CACHE = "_psnr_per_sample"         # key of the per-sample PSNR values the device metric kernel produced for an output dict
 
 
 class _RankShard(torch.utils.data.Sampler):
@@ -107,6 +110,10 @@ class DenoiserTrainer:
         self.accumulate = 1
         # evaluation also reports SSIM (`ssdn eval --ssim`): ssim_out / ssim_mu_out next to the PSNRs.  A plain attribute, not a ConfigValue
         self.ssim = False
+        # ... and the calibration of the posterior covariance (`ssdn eval --calibration`, SSDN pipeline only): calib_nll, calib_maha,
+        # calib_rmse_ratio, calib_cover_2s.  calibration_hist: the z-score histogram [C,34] summed over the last such evaluation
+        self.calibration = False
+        self.calibration_hist = None
 
     # ---- target -----------------------------------------------------------------------------------------------------------
     @property
@@ -283,6 +290,12 @@ class DenoiserTrainer:
                     outputs[_SSIM_CACHE] = per = self.calculate_ssim(data, outputs)
                     for name in self.img_outputs(prefix="ssim").values():
                         eval_history[name] += per[name]
+                if self.calibration:
+                    outputs[_CALIB_CACHE] = cal = self.calculate_calibration(data, outputs)
+                    for name in CALIB_METRICS:
+                        eval_history["calib_" + name] += cal[name]
+                    total = cal["hist"].sum(0)
+                    self.calibration_hist = total if idx == 0 or self.calibration_hist is None else self.calibration_hist + total
                 if output_callback:
                     output_callback(idx, outputs)
                 idx += image_count
@@ -354,8 +367,8 @@ class DenoiserTrainer:
 
     @staticmethod
     def _metric_strs(md) -> list:
-        # (an SSIM lives in [-1, 1]: four decimals where the other metrics print two)
-        return [("{}={:8.4f}" if str(k).startswith("ssim") else "{}={:8.2f}").format(k, float(torch.as_tensor(m.accumulated()).float().mean()))
+        # (an SSIM lives in [-1, 1], a calibration value near 1: four decimals where the other metrics print two)
+        return [("{}={:8.4f}" if str(k).startswith(("ssim", "calib_")) else "{}={:8.2f}").format(k, float(torch.as_tensor(m.accumulated()).float().mean()))
                 for k, m in md.items() if isinstance(m, Metric) and not m.empty()]
 
     def train_state_str(self) -> str:
@@ -399,6 +412,24 @@ class DenoiserTrainer:
         imgs.update({name: outputs[key] for key, name in self.img_outputs(prefix="ssim").items()})
         return {name: torch.stack([ssdn.utils.calculate_ssim(a.cpu(), b.cpu()) for a, b in zip(NoisyDataset.unpad(img, metadata), clean)])
                 for name, img in imgs.items()}
+
+    def calculate_calibration(self, data, outputs: Dict) -> Dict[str, Tensor]:
+        """Denoiser.calibration's dict with the histogram for the batch just run: host float64 [B] values, "stats" [B,12], "hist"
+        [B,C,34].  On a GPU one Denoiser.calibration call (SSDN_OP_CALIBRATION); otherwise ssdn.utils.calculate_calibration on each
+        un-padded (IMG_DENOISED, posterior covariance, clean) triple, the covariance from the output dict or Denoiser.posterior."""
+        if self.cfg[ConfigValue.PIPELINE] != Pipeline.SSDN:
+            raise NotImplementedError("calibration: the %s pipeline has no posterior covariance (SSDN pipeline only)" % self.cfg[ConfigValue.PIPELINE].value)
+        if getattr(self.denoiser, "device", torch.device("cpu")).type == "cuda":
+            return self.denoiser.calibration(data, hist=True)
+        metadata = data[NoisyDataset.METADATA]
+        cov = outputs[_POSTERIOR_COV] if _POSTERIOR_COV in outputs else self.denoiser.posterior(data)["cov"]
+        mean, clean = outputs[PipelineOutput.IMG_DENOISED], metadata[NoisyDataset.Metadata.CLEAN]
+        shp = metadata.get(NoisyDataset.Metadata.IMAGE_SHAPE)
+        per = []
+        for b in range(mean.shape[0]):          # (the covariance has C(C+1)/2 planes: cropped here, NoisyDataset.unpad would cut them to C)
+            h, w = (int(v) for v in shp[b][-2:]) if shp is not None else mean.shape[-2:]
+            per.append(ssdn.utils.calculate_calibration(*(t[b:b + 1, :, :h, :w].cpu() for t in (mean, cov, clean)), hist=True))
+        return {k: torch.cat([p[k] for p in per]) for k in per[0]}
 
     @staticmethod
     def calculate_psnr(outputs: Dict, output: PipelineOutput, unpad: bool = True) -> Tensor:

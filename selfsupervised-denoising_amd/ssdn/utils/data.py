@@ -1,4 +1,7 @@
 """Tensor helpers used on / next to the hot path (drop-in for the used part of /root/reference/ssdn/ssdn/utils/data.py)."""
+import math
+from typing import Dict
+
 import torch
 from torch import Tensor
 
@@ -80,6 +83,114 @@ def calculate_ssim(img: Tensor, ref: Tensor, full: bool = False):
     if single:
         val, smap = val[0], smap[0]
     return (val, smap) if full else val
+
+
+# the chi^2_C quantiles at 0.5, 0.9 and 0.99 (C = 1: erf(sqrt(x/2)) = p; C = 3: erf(sqrt(x/2)) - sqrt(2x/pi) exp(-x/2) = p) and the
+# nominal levels the counts of |z| <= 1, 2, 3 are judged against, erf(k / sqrt 2)
+CALIB_CHI2_LEVELS = (0.5, 0.9, 0.99)
+CALIB_CHI2 = {1: (0.45493642311957, 2.70554345409541, 6.63489660102120), 3: (2.36597388437534, 6.25138863117032, 11.3448667301444)}
+CALIB_SIGMA_LEVELS = (0.6826894921370859, 0.9544997361036416, 0.9973002039367398)
+CALIB_NSTATS, CALIB_HIST_BINS = 12, 34
+CALIB_VALUES = ("nll", "maha", "rmse_ratio", "cover_1s", "cover_2s", "cover_3s", "cover_50", "cover_90", "cover_99", "degenerate")
+
+
+def calibration_values(stats: Tensor, channels: int) -> Dict[str, Tensor]:
+    """The reported calibration values from the raw statistics [..., 12] (float64) of calculate_calibration / SSDN_OP_CALIBRATION:
+    nll = (sum d2 + sum logdet) / (2 N C) + ln(2 pi) / 2 (nats per pixel-channel of the clean image under the posterior), maha =
+    sum d2 / (N C) (ideal 1; above 1 the model is over-confident), rmse_ratio = sqrt(sum |r|^2 / sum tr S) (actual over predicted RMSE),
+    cover_1s/2s/3s = counts / (N C), cover_50/90/99 = counts / N, degenerate = degenerate / (N + degenerate).  N = 0: the ratios are NaN."""
+    s = stats.to(torch.float64)
+    nan = torch.full_like(s[..., 0], float("nan"))
+    n, deg = s[..., 0], s[..., 1]
+    some = n > 0
+    nc = torch.where(some, n * channels, nan)
+    res = {"nll": 0.5 * (s[..., 2] + s[..., 3]) / nc + 0.5 * math.log(2 * math.pi), "maha": s[..., 2] / nc,
+           "rmse_ratio": torch.where(some, torch.sqrt(s[..., 4] / torch.where(some, s[..., 5], nan)), nan)}
+    for k, name in enumerate(("cover_1s", "cover_2s", "cover_3s")):
+        res[name] = s[..., 6 + k] / nc
+    for k, name in enumerate(("cover_50", "cover_90", "cover_99")):
+        res[name] = s[..., 9 + k] / torch.where(some, n, nan)
+    res["degenerate"] = torch.where(n + deg > 0, deg / torch.where(n + deg > 0, n + deg, nan), nan)
+    return res
+
+
+def calculate_calibration(mean: Tensor, cov: Tensor, ref: Tensor, hist: bool = False, zmap: bool = False) -> Dict[str, Tensor]:
+    """Per-sample calibration of a per-pixel Gaussian posterior N(mean, S) against the clean image -- the specification
+    SSDN_OP_CALIBRATION (csrc/calibration.hip) is held to, float64 on any device.  mean, ref: [B,C,H,W]; cov: [B, C(C+1)/2, H, W] in
+    SSDN_OP_HEAD_POSTERIOR's order (00, 01, 02, 11, 12, 22; C = 1: the variance), C in {1, 3}; the caller crops to the un-padded
+    extent, as with calculate_ssim.  Per pixel, in float64 from the inputs as they are, r = ref - mean and, in this fixed order (C = 3),
+        p0 = s00, l00 = sqrt p0, l10 = s01 / l00, l20 = s02 / l00;  p1 = s11 - l10^2, l11 = sqrt p1, l21 = (s12 - l20 l10) / l11;
+        p2 = s22 - l20^2 - l21^2, l22 = sqrt p2;  w0 = r0 / l00, w1 = (r1 - l10 w0) / l11, w2 = (r2 - l20 w0 - l21 w1) / l22;
+        d2 = w0^2 + w1^2 + w2^2, logdet = ln p0 + ln p1 + ln p2   (C = 1: d2 = r^2 / s, logdet = ln s),   z_c = r_c / sqrt(s_cc).
+    A pixel is valid iff all its inputs are finite, every pivot p_k > 0 and every s_cc > 0; a degenerate pixel is counted and left out
+    of everything else.  -> {"stats": float64 [B,12]: N, degenerate, sum d2, sum logdet, sum |r|^2, sum tr S, the (valid pixel, channel)
+    pairs with |z_c| <= 1, 2, 3, the valid pixels with d2 <= the chi^2_C quantile at 0.5, 0.9, 0.99 (CALIB_CHI2)} and the values
+    `calibration_values` derives from them, float64 [B] each.  hist=True adds "hist", int64 [B,C,34]: counts of z_c over the valid
+    pixels (bin 0: z < -4; bin 1 + floor(4 z + 16): -4 <= z < 4; bin 33: z >= 4); zmap=True adds "zmap", float64 [B,C,H,W], NaN at
+    degenerate pixels.
+    For an impulse model the posterior is a two-component mixture and `cov` its moment-matched covariance (Denoiser.posterior): the
+    statistics describe that Gaussian, not the mixture."""
+    if mean.dim() != 4 or mean.shape != ref.shape or mean.shape[1] not in (1, 3):
+        raise ValueError("calculate_calibration: mean and ref must be BCHW of one shape with C in {1, 3}, got %s and %s"
+                         % (tuple(mean.shape), tuple(ref.shape)))
+    B, C, H, W = mean.shape
+    if tuple(cov.shape) != (B, C * (C + 1) // 2, H, W):
+        raise ValueError("calculate_calibration: cov must be %s, got %s" % ((B, C * (C + 1) // 2, H, W), tuple(cov.shape)))
+    m, s, y = mean.to(torch.float64), cov.to(torch.float64), ref.to(torch.float64)
+    fin = torch.isfinite(m).all(1) & torch.isfinite(s).all(1) & torch.isfinite(y).all(1)
+    r = y - m
+    if C == 3:
+        r0, r1, r2 = r[:, 0], r[:, 1], r[:, 2]
+        s00, s01, s02, s11, s12, s22 = (s[:, k] for k in range(6))
+        p0 = s00
+        l00 = torch.sqrt(p0)
+        l10, l20 = s01 / l00, s02 / l00
+        p1 = s11 - l10 * l10
+        l11 = torch.sqrt(p1)
+        l21 = (s12 - l20 * l10) / l11
+        p2 = (s22 - l20 * l20) - l21 * l21
+        l22 = torch.sqrt(p2)
+        w0 = r0 / l00
+        w1 = (r1 - l10 * w0) / l11
+        w2 = ((r2 - l20 * w0) - l21 * w1) / l22
+        d2 = (w0 * w0 + w1 * w1) + w2 * w2
+        logdet = (torch.log(p0) + torch.log(p1)) + torch.log(p2)
+        valid = fin & (p0 > 0) & (p1 > 0) & (p2 > 0) & (s11 > 0) & (s22 > 0)
+        rr = (r0 * r0 + r1 * r1) + r2 * r2
+        tr = (s00 + s11) + s22
+        z = torch.stack([r0 / torch.sqrt(s00), r1 / torch.sqrt(s11), r2 / torch.sqrt(s22)], 1)
+    else:
+        r0, s00 = r[:, 0], s[:, 0]
+        valid = fin & (s00 > 0)
+        d2 = (r0 * r0) / s00
+        logdet = torch.log(s00)
+        rr, tr = r0 * r0, s00
+        z = (r0 / torch.sqrt(s00))[:, None]
+    zero = torch.zeros((), dtype=torch.float64, device=m.device)
+
+    def total(v):                       # over the valid pixels of each sample
+        return torch.where(valid, v, zero).reshape(B, -1).sum(1)
+
+    def count(mask):
+        return mask.reshape(B, -1).sum(1).to(torch.float64)
+    vc = valid[:, None]
+    az = z.abs()
+    cols = [count(valid), count(~valid), total(d2), total(logdet), total(rr), total(tr)]
+    cols += [count(vc & (az <= k)) for k in (1.0, 2.0, 3.0)]
+    cols += [count(valid & (d2 <= q)) for q in CALIB_CHI2[C]]
+    stats = torch.stack(cols, 1)
+    res = {"stats": stats}
+    res.update(calibration_values(stats, C))
+    if hist:
+        zz = torch.where(vc, z, zero)
+        bins = torch.where(zz < -4.0, torch.zeros_like(zz), torch.where(zz >= 4.0, torch.full_like(zz, CALIB_HIST_BINS - 1),
+                                                                        1 + torch.floor(4.0 * zz + 16.0))).to(torch.int64)
+        onehot = torch.zeros((B, C, CALIB_HIST_BINS), dtype=torch.int64, device=m.device)
+        onehot.scatter_add_(2, bins.reshape(B, C, -1), vc.expand(B, C, H, W).reshape(B, C, -1).to(torch.int64))
+        res["hist"] = onehot
+    if zmap:
+        res["zmap"] = torch.where(vc, z, torch.full_like(z, float("nan")))
+    return res
 
 
 # ---- image I/O helpers of the trainer / evaluator (utils/data.py:69-125) ------------------------------------------------------
