@@ -333,6 +333,32 @@ int ssdn_run_ops(const ssdn_op* ops, int n, void* stream) {
                 while (m < WREDUCE_MULTI_MAX && i + m < n && ops[i + m].type == SSDN_OP_WREDUCE && ops[i + m].args &&
                        (one_lane ? 0 : ops[i + m].lane) == lane)
                     items[m] = (const ssdn_wreduce_args*)ops[i + m].args, ++m;
+                // ... and when the whole run is directly followed by SSDN_OP_ADAM with its whole run of re-packs -- the end of a single-GPU
+                // training step -- all of it is ONE launch that only reads the slabs (tail_fused.hip)
+                static const bool no_tail = ssdn_tuning_env("SSDN_NO_TAIL_FUSE") != nullptr;      // A/B aid, read once
+                const int ia = i + m;                       // the op behind the run
+                const bool more_red = ia < n && ops[ia].type == SSDN_OP_WREDUCE && (one_lane ? 0 : ops[ia].lane) == lane;      // (run cut at the table size)
+                if (!no_tail && !more_red && ia < n && ops[ia].type == SSDN_OP_ADAM && ops[ia].args && (one_lane ? 0 : ops[ia].lane) == lane) {
+                    const ssdn_wpack_args* packs[ADAM_PACK_MAX];
+                    int mp = 0;
+                    while (mp < ADAM_PACK_MAX && ia + 1 + mp < n && ops[ia + 1 + mp].type == SSDN_OP_WPACK && ops[ia + 1 + mp].args &&
+                           (one_lane ? 0 : ops[ia + 1 + mp].lane) == lane)
+                        packs[mp] = (const ssdn_wpack_args*)ops[ia + 1 + mp].args, ++mp;
+                    const bool whole_run = !(ia + 1 + mp < n && ops[ia + 1 + mp].type == SSDN_OP_WPACK);      // (never split a run of re-packs)
+                    const ssdn_adam_args* ad = (const ssdn_adam_args*)ops[ia].args;
+                    if (mp > 0 && whole_run && adam_pack_fusable(ad, packs, mp)) {
+                        const int ok = tail_fused_ok(items, m, ad, packs, mp);
+                        if (ok < 0) return -1;
+                        if (ok) {
+                            // (the ops skipped are this lane's: the lane's state above already stands for all of them; if they end a side
+                            //  lane the one launch carries the join's stop event, as the run's stage 2 would)
+                            arm_last(ia + 1 + mp);
+                            rc = launch_tail_fused(items, m, ad, packs, mp, s);
+                            i = ia + mp;
+                            break;
+                        }
+                    }
+                }
                 arm_last(i + m);
                 rc = m > 1 ? launch_wreduce_multi(items, m, s) : launch_wreduce((const ssdn_wreduce_args*)p, s);
                 i += m - 1;

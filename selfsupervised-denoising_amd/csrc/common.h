@@ -155,6 +155,9 @@ int launch_adam(const ssdn_adam_args* a, hipStream_t s);
 #define ADAM_PACK_MAX 24
 int adam_pack_fusable(const ssdn_adam_args* a, const ssdn_wpack_args* const* items, int n);
 int launch_adam_pack(const ssdn_adam_args* a, const ssdn_wpack_args* const* items, int n, hipStream_t s);
+// tail_fused.hip: a run of reductions directly followed by Adam and its whole run of re-packs as ONE launch (slabs only read)
+int tail_fused_ok(const ssdn_wreduce_args* const* wr, int nw, const ssdn_adam_args* a, const ssdn_wpack_args* const* wp, int np);   // 1: yes, 0: no, < 0: error
+int launch_tail_fused(const ssdn_wreduce_args* const* wr, int nw, const ssdn_adam_args* a, const ssdn_wpack_args* const* wp, int np, hipStream_t s);
 int launch_metrics(const ssdn_metrics_args* a, hipStream_t s);
 int launch_accum(const ssdn_accum_args* a, hipStream_t s);
 int launch_noise(const ssdn_noise_args* a, hipStream_t s);

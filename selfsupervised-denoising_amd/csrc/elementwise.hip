@@ -1,8 +1,8 @@
 // elementwise.hip -- HBM-bound layout / routing kernels of the blind-spot U-Net (gfx950).
 // All activation traffic is NHWC fp16 moved as 16-byte (8-channel) vectors per lane.
 #include "common.h"
+#include "adam_pack.h"      // EW_BLOCK, wpack_cm, the Adam element and the Adam + re-pack tile (shared with tail_fused.hip)
 
-#define EW_BLOCK 256
 static inline int ew_grid(long long n) {
     long long g = (n + EW_BLOCK - 1) / EW_BLOCK;
     return (int)(g < 1 ? 1 : g);
@@ -343,14 +343,6 @@ static __device__ __forceinline__ int k_to_cin(int k, int c0, int c1_real) {
     int r = k - c0;
     return r < c1_real ? c0 + r : -1;
 }
-// position of element (tap t, row m, column k) in the chunk-major pre-swizzled copy [tap][chunk][rows][kc] (ssdn_conv_args.wc)
-static __device__ __forceinline__ long long wpack_cm(int t, int m, int k, int rows, int K) {
-    const int nfull = K / 48;
-    const int c = k / 48 < nfull ? k / 48 : nfull;
-    const int kk = k - c * 48, kcw = c < nfull ? 48 : 16;
-    const int piece = (kk >> 3) ^ ((m >> 3) & 1);
-    return (long long)t * rows * K + (long long)c * 48 * rows + (long long)m * kcw + piece * 8 + (kk & 7);
-}
 static __device__ __forceinline__ void wpack_element(const ssdn_wpack_args& a, long long idx) {
     long long nf = (long long)a.ntaps * a.Mpad_f * a.Ktot;
     long long nd = a.wd ? (long long)a.ntaps * a.Mpad_d * a.Kd : 0;
@@ -604,23 +596,7 @@ int launch_accum(const ssdn_accum_args* a, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // ADAM  (train.py:100-107,202): one fused pass over the flat master buffer
 // ------------------------------------------------------------------------------------------------
-// one element of the Adam update (shared by k_adam and k_adam_pack: the two must round identically; explicit fmaf / no re-association)
-struct AdamIn { float g, m, v, p; };
-static __device__ __forceinline__ AdamIn adam_load(const ssdn_adam_args& a, long long i) { return AdamIn{a.g[i], a.m[i], a.v[i], a.p[i]}; }
-static __device__ __forceinline__ float adam_apply(const ssdn_adam_args& a, long long i, const AdamIn& q, float inv_bc2s, float step) {
-    const float g = q.g * a.gscale;
-    const float m = __fmaf_rn(a.b1, q.m, __fmul_rn(1.f - a.b1, g));
-    const float v = __fmaf_rn(a.b2, q.v, __fmul_rn(__fmul_rn(1.f - a.b2, g), g));
-    a.m[i] = m;
-    a.v[i] = v;
-    const float den = __fmaf_rn(sqrtf(v), inv_bc2s, a.eps);
-    const float pn = __fsub_rn(q.p, __fdiv_rn(__fmul_rn(step, m), den));
-    a.p[i] = pn;
-    return pn;
-}
-static __device__ __forceinline__ float adam_elem(const ssdn_adam_args& a, long long i, float inv_bc2s, float step) {
-    return adam_apply(a, i, adam_load(a, i), inv_bc2s, step);
-}
+// (one element of the Adam update: adam_pack.h)
 __global__ void k_adam(ssdn_adam_args a) {
     long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     long long stride = (long long)gridDim.x * blockDim.x;
@@ -636,8 +612,6 @@ __global__ void k_adam(ssdn_adam_args a) {
 // without shadows (biases, the learnable sigma).  The tile is read in master order (OIHW: runs of 48 x ntaps floats), updated, parked in
 // LDS and written out in SHADOW order: [tap][row][k] runs of 96 bytes for the forward shadows, 16-byte pieces (8 consecutive output
 // channels) for the transposed data-gradient shadows.  (One thread per parameter scattered 2-byte stores over four tensors: 31 us.)
-#define AP_TM 8
-#define AP_TK 48
 struct AdamPackTable {
     ssdn_adam_args a;
     ssdn_wpack_args e[ADAM_PACK_MAX];
@@ -651,60 +625,12 @@ struct AdamPackTable {
 };
 template <int NT>
 static __device__ __forceinline__ void adam_pack_tile(const AdamPackTable& t, int j, int tile, float* lds, float inv_bc2s, float step) {
-    const ssdn_adam_args& a = t.a;
     const ssdn_wpack_args& w = t.e[j];
     const int tk = t.tiles_k[j];
     const int mo0 = (tile / tk) * AP_TM, k0 = (tile % tk) * AP_TK;
-    const int tid = threadIdx.x;
-    // phase 1: master order; the loads of up to 7 elements of a thread are in flight together (one element at a time was a chain of 14
-    // exposed HBM round trips per thread)
-    constexpr int TOTAL = AP_TM * AP_TK * NT, NIT = (TOTAL + EW_BLOCK - 1) / EW_BLOCK, BATCH = NIT < 7 ? NIT : 7;
-#pragma unroll
-    for (int it0 = 0; it0 < NIT; it0 += BATCH) {
-        AdamIn q[BATCH];
-        long long idx[BATCH];
-        bool ok[BATCH];
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-            const int e = tid + (it0 + u) * EW_BLOCK;
-            const int mo = e / (AP_TK * NT), r = e - mo * (AP_TK * NT);
-            const int kk = r / NT, tp = r - kk * NT;
-            ok[u] = it0 + u < NIT && e < TOTAL && mo0 + mo < w.M && k0 + kk < w.cin;
-            idx[u] = ok[u] ? t.w_off[j] + ((long long)(mo0 + mo) * w.cin + k0 + kk) * NT + tp : t.w_off[j];
-            q[u] = adam_load(a, idx[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < BATCH; ++u) {
-            const int e = tid + (it0 + u) * EW_BLOCK;
-            if (it0 + u >= NIT || e >= TOTAL) continue;
-            const int mo = e / (AP_TK * NT), r = e - mo * (AP_TK * NT);
-            const int kk = r / NT, tp = r - kk * NT;
-            lds[(tp * AP_TM + mo) * (AP_TK + 1) + kk] = ok[u] ? adam_apply(a, idx[u], q[u], inv_bc2s, step) : 0.f;
-        }
-    }
+    adam_pack_update<NT, AP_TK>(t.a, w, t.w_off[j], mo0, k0, lds, inv_bc2s, step, ApGradFromMemory{t.a.g});      // (adam_pack.h)
     __syncthreads();
-    // phase 2a: forward shadows, k fastest
-    for (int e = tid; e < NT * AP_TM * AP_TK; e += EW_BLOCK) {
-        const int tp = e / (AP_TM * AP_TK), r = e - tp * (AP_TM * AP_TK);
-        const int mo = r / AP_TK, kk = r - mo * AP_TK;
-        const int m = mo0 + mo, k = k0 + kk;
-        if (m >= w.M || k >= w.cin) continue;
-        const float pn = lds[(tp * AP_TM + mo) * (AP_TK + 1) + kk];
-        ((h16*)w.wf)[((long long)tp * w.Mpad_f + m) * w.Ktot + k] = (h16)pn;
-        if (w.wfc) ((h16*)w.wfc)[wpack_cm(tp, m, k, w.Mpad_f, w.Ktot)] = (h16)pn;
-    }
-    // phase 2b: data-gradient shadows (transposed), output channel fastest
-    if (w.wd) {
-        for (int e = tid; e < NT * AP_TK * AP_TM; e += EW_BLOCK) {
-            const int tp = e / (AP_TK * AP_TM), r = e - tp * (AP_TK * AP_TM);
-            const int kk = r / AP_TM, mo = r - kk * AP_TM;
-            const int m = mo0 + mo, k = k0 + kk;
-            if (m >= w.M || k >= w.cin || k >= w.Mpad_d || m >= w.Kd) continue;   // (the shadow may cover fewer input slots: decode_block_1.0's image channels need no gradient)
-            const float pn = lds[(tp * AP_TM + mo) * (AP_TK + 1) + kk];
-            ((unsigned short*)w.wd)[((long long)tp * w.Mpad_d + k) * w.Kd + m] = f2bf(pn);
-            if (w.wdc) ((unsigned short*)w.wdc)[wpack_cm(tp, k, m, w.Mpad_d, w.Kd)] = f2bf(pn);
-        }
-    }
+    adam_pack_store<NT, AP_TK>(w, mo0, k0, lds);
 }
 __global__ void k_adam_pack(AdamPackTable t) {
     __shared__ float lds[9 * AP_TM * (AP_TK + 1)];
