@@ -758,6 +758,13 @@ int ssdn_conv_fuses_unrot(const ssdn_conv_args* a);
 int ssdn_conv_fuses_urot(const ssdn_conv_args* a);
 /* 1 if SSDN_OP_CONV with these arguments writes sign_out / reads mask_sign (whichever are set), 0 if it cannot. */
 int ssdn_conv_signs(const ssdn_conv_args* a);
+/* 1 if SSDN_OP_CONV with these arguments runs k_conv16 (csrc/conv16.hip): a 3x3 layer of 96 output channels (144 in the data-gradient
+ * role) on whole 16x16 images, 96 or 144 input channels in 48-channel chunks, at most one image per CU, 16-bit output, no fused output
+ * but the up-sum -- the launches that would otherwise run k_conv's flat path; the result is bit-identical to that path's.  Host code only.
+ * ssdn_conv_set_conv16(roles): bit 0 = the forward role may run k_conv16, bit 1 = the data-gradient role may; 0 leaves every launch on
+ * k_conv (test and A/B aid); -1 restores the default (the data-gradient role: profiles/conv16_ab.txt). */
+int ssdn_conv16_eligible(const ssdn_conv_args* a);
+int ssdn_conv_set_conv16(int roles);
 
 /* ssdn_run_ops executes a run of consecutive ops on one lane as ONE launch (k_conv_chain, csrc/conv_chain.hip: one workgroup per
  * image walks all layers with every tensor of the run resident in LDS) when the run is a "chain":

@@ -180,6 +180,11 @@ bool conv_fuses_unrot(const ssdn_conv_args* a);                // conv_mfma.hip:
 bool conv_fuses_upsum(const ssdn_conv_args* a);                // conv_mfma.hip: k_cdma or the flat path applies the fused UPSUM_BWD
 bool conv_fuses_pool(const ssdn_conv_args* a);                  // conv_mfma.hip: the launch takes the flat path (fused max-pool)
 int launch_conv_dma(const ssdn_conv_args* a, hipStream_t s);
+// conv16.hip: the 96-channel 3x3 layers at 16x16 pixels on a resident half-image tile (k_conv16)
+bool conv16_shape_ok(const ssdn_conv_args* a);                 // the kernel's shape class and epilogue flags (host code only)
+bool conv_use_conv16(const ssdn_conv_args* a);                 // conv_mfma.hip: launch_conv runs `a` on k_conv16
+int conv16_lds_bytes(const ssdn_conv_args* a);
+int launch_conv16(const ssdn_conv_args* a, hipStream_t s);
 // conv_thin.hip: forward 3x3 layer with 1..3 real input channels (encode_block_1.0) as an im2col-shaped GEMM
 bool conv_thin_eligible(const ssdn_conv_args* a);
 bool conv_thin_fuses_pack(const ssdn_pack_input_args* pk, const ssdn_conv_args* a);   // (the conv must still pass launch_conv's own routing)

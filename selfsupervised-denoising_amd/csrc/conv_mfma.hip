@@ -786,6 +786,22 @@ extern "C" int ssdn_conv_set_mode(int mode) {
 static bool conv_use_dma(const ssdn_conv_args* a) { return g_conv_mode > 0 && !a->pool.p && conv_dma_eligible(a, g_conv_mode == 2); }
 static bool conv_use_gemm(const ssdn_conv_args* a) { return g_conv_mode > 0 && gemm_dma_eligible(a); }
 static bool conv_use_thin(const ssdn_conv_args* a) { return g_conv_mode > 0 && conv_thin_eligible(a); }
+static bool conv_flat_path(const ssdn_conv_args* a);
+// k_conv16 (conv16.hip) takes, of the launches that would run k_conv's flat path, the 96-channel layers at 16x16 pixels; bit 0 of the
+// roles: forward, bit 1: data gradient (ssdn_conv_set_conv16: 0 leaves every launch where it was -- test and A/B aid; -1: the default).
+// Default: the data gradient only.  Forward measured no faster than k_conv (profiles/conv16_ab.txt: both stream the whole weight tensor
+// into every one of 256 CUs at once, and that stream is the launch); the kernel serves it when asked.
+#define CONV16_DEFAULT_ROLES 2
+static int g_conv16_roles = CONV16_DEFAULT_ROLES;
+extern "C" int ssdn_conv_set_conv16(int roles) {
+    if (roles < -1 || roles > 3) return ssdn_set_error("conv16 roles must be -1 .. 3");
+    g_conv16_roles = roles < 0 ? CONV16_DEFAULT_ROLES : roles;
+    return 0;
+}
+bool conv_use_conv16(const ssdn_conv_args* a) {
+    return g_conv_mode > 0 && (g_conv16_roles & (a->bf16 ? 2 : 1)) && !conv_validate(a) && conv16_shape_ok(a) && !conv_use_gemm(a) &&
+           !conv_use_thin(a) && !conv_use_dma(a) && conv_flat_path(a);
+}
 bool conv_gradpack_fusable(const ssdn_grad_pack_args* gp, const ssdn_conv_args* a) {
     return !conv_validate(a) && !conv_use_gemm(a) && !conv_use_thin(a) && !conv_use_dma(a) && gradpack_dgrad_fusable(gp, a);
 }
@@ -826,6 +842,7 @@ int conv_lds_bytes(const ssdn_conv_args* a) {
     if (conv_use_gemm(a)) return gemm_dma_lds_bytes(a);
     if (conv_use_thin(a)) return 32 * 1024;                     // (halo of four channel slots + four wave-private transpose tiles: < 32 KB)
     if (conv_use_dma(a)) return conv_dma_lds_bytes(a->Mpad >= 96 ? 3 : a->Mpad / 32);
+    if (conv_use_conv16(a)) return conv16_lds_bytes(a);
     ConvGeom g = conv_geom(a->ltw, a->lth, a->ltn, a->ntaps, a->dy, a->dx, a->N, a->H, a->W, a->kc);
     int mt = a->Mpad / 32;
     if (mt > 3) mt = 3;
@@ -941,6 +958,7 @@ int launch_conv(const ssdn_conv_args* a, hipStream_t s) {
     if (conv_use_gemm(a)) return launch_gemm_dma(a, s);
     if (conv_use_thin(a)) return launch_conv_thin(a, nullptr, s);
     if (conv_use_dma(a)) return launch_conv_dma(a, s);
+    if (conv_use_conv16(a)) return launch_conv16(a, s);
     ConvGeom g = conv_geom(a->ltw, a->lth, a->ltn, a->ntaps, a->dy, a->dx, a->N, a->H, a->W, a->kc);
     ConvAux x;
     x.mg_hw = magic_of(g.HW);

@@ -192,7 +192,7 @@ SYMBOLS = ["ssdn_run_ops", "ssdn_stream_order", "ssdn_conv_lds_bytes", "ssdn_wgr
            "ssdn_device_cus", "ssdn_probe_mfma", "ssdn_probe_tr16", "ssdn_struct_size", "ssdn_profile_enable",
            "ssdn_profile_read", "ssdn_profile_set_stride", "ssdn_debug_set_trace", "ssdn_debug_get_trace", "ssdn_conv_set_mode",
            "ssdn_wgrad_mergeable", "ssdn_conv_fuses_pool", "ssdn_conv_fuses_upsum", "ssdn_conv_fuses_unrot", "ssdn_conv_fuses_urot", "ssdn_conv_signs", "ssdn_chain_len",
-           "ssdn_conv_set_chain", "ssdn_wgrad_mega_ok", "ssdn_wgrad_variant",
+           "ssdn_conv_set_chain", "ssdn_wgrad_mega_ok", "ssdn_wgrad_variant", "ssdn_conv16_eligible", "ssdn_conv_set_conv16",
            "ssdn_plan_load", "ssdn_plan_destroy", "ssdn_plan_arena_bytes", "ssdn_plan_meta", "ssdn_plan_bind", "ssdn_plan_tensor", "ssdn_plan_run",
            "ssdn_plan_set_lr", "ssdn_net_forward", "ssdn_train_step"]
 PLAN_PHASES = dict(repack=0, forward=1, backward=2, optimiser=3)
@@ -264,6 +264,11 @@ def load() -> C.CDLL:
     lib.ssdn_conv_fuses_upsum.restype = C.c_int
     lib.ssdn_conv_fuses_pool.argtypes = [C.c_void_p]
     lib.ssdn_conv_fuses_pool.restype = C.c_int
+    if hasattr(lib, "ssdn_conv16_eligible"):     # (older builds loaded through SSDN_HIP_LIB have no k_conv16)
+        lib.ssdn_conv16_eligible.argtypes = [C.c_void_p]
+        lib.ssdn_conv16_eligible.restype = C.c_int
+        lib.ssdn_conv_set_conv16.argtypes = [C.c_int]
+        lib.ssdn_conv_set_conv16.restype = C.c_int
     lib.ssdn_wgrad_mergeable.argtypes = [C.c_void_p]
     lib.ssdn_wgrad_mergeable.restype = C.c_int
     lib.ssdn_wgrad_mega_ok.argtypes = [C.c_void_p]
@@ -296,6 +301,8 @@ def load() -> C.CDLL:
         raise SsdnHipError("libssdn_hip.so ABI version mismatch")
     if os.environ.get("SSDN_CHAIN_MODE"):        # A/B aid (tools/): ssdn_conv_set_chain before any plan is made -- 0 off, 1 default, 2 see conv_chain.hip
         lib.ssdn_conv_set_chain(int(os.environ["SSDN_CHAIN_MODE"]))
+    if os.environ.get("SSDN_CONV16_ROLES") and hasattr(lib, "ssdn_conv_set_conv16"):      # A/B aid: k_conv16 for no role (0), forward (1), data gradient (2), both (3)
+        lib.ssdn_conv_set_conv16(int(os.environ["SSDN_CONV16_ROLES"]))
     _lib = lib
     return lib
 
