@@ -86,7 +86,8 @@ enum ssdn_op_type {
  * of WAR/WAW hazards between lanes: lanes 1 and 3 carry (alternately) the weight-gradient GEMMs of the backward pass (they
  * read tensors written once per step and write their OWN slab), lane 2 the slab reductions (they read that slab and write
  * the flat gradient, which nothing else touches) -- so the many small, latency-bound backward launches overlap instead of
- * queueing behind each other. */
+ * queueing behind each other.  (The planner's guarantee is checked, channel range by channel range, by
+ * tests/test_lane_hazards_cpu.py against the model in tests/lane_model.py; the executor's ordering by tests/test_hip_lanes.py.) */
 typedef struct ssdn_op {
     int32_t type;
     int32_t lane;

@@ -42,8 +42,12 @@ def _unpack_signs(b, C):
 
 
 class Interp:
-    def __init__(self, plan, flat_params: torch.Tensor, fp16: bool = False):
+    def __init__(self, plan, flat_params: torch.Tensor, fp16: bool = False, record: bool = False):
+        """record: keep, per executed op, the set of (tensor, lo, hi, "r" / "w") regions it touched in `self.rec` (tests/lane_model.py
+        says what the units are: channels of a View, blocks of a slab, elements of the flat buffers, (0, WHOLE) otherwise).  Recording
+        only observes: every value computed is the same with and without it."""
         self.plan, self.fp16 = plan, fp16
+        self.rec = [] if record else None
         self.params = flat_params.clone().to(torch.get_default_dtype())
         self.grads = torch.zeros_like(self.params)
         self.t = {}
@@ -51,9 +55,20 @@ class Interp:
         self.slabs, self.bslabs = {}, {}      # slab tensor name -> one block per mblock of its weight-gradient launch (any legal order of the list runs)
         self.L = {l.name: l for l in plan.layers}
 
-    # ---- tensor access ---------------------------------------------------------------------------------
+    # ---- tensor access: every op reaches its tensors through these (so that a recording run sees all of it) ----------------------
+    WHOLE = 1 << 62
+
+    def _note(self, name, lo, hi, mode):
+        if self.rec is not None:
+            self.rec[-1].add((name, int(lo), int(hi), mode))
+
     def view(self, v, c):
         """channels [co, co+c) of an act tensor"""
+        self._note(v.t, v.co, v.co + c, "r")
+        return self.t[v.t][..., v.co:v.co + c]
+
+    def _own(self, v, c):
+        """what THIS op has just stored through `v` (a fused epilogue works on the stored, rounded values): no read of its own"""
         return self.t[v.t][..., v.co:v.co + c]
 
     def alloc(self, name):
@@ -63,21 +78,36 @@ class Interp:
         return self.t[name]
 
     def store(self, v, c, val):
+        self._note(v.t, v.co, v.co + c, "w")
         self.alloc(v.t)[..., v.co:v.co + c] = _r16(val, self.fp16, self.plan.tensors[v.t].kind)
 
-    def weight(self, lname):
+    def get(self, name):
+        """a tensor addressed by name, read as a whole"""
+        self._note(name, 0, self.WHOLE, "r")
+        return self.t[name]
+
+    def put(self, name, val):
+        """a tensor addressed by name, written as a whole"""
+        self._note(name, 0, self.WHOLE, "w")
+        self.t[name] = val
+
+    def weight(self, lname, bias=False):
+        """the master weights [M, cin, ntaps] of a layer, or (bias=True) its bias"""
         l = self.L[lname]
-        w = self.params[self.plan.param_base + l.w_off: self.plan.param_base + l.w_off + l.M * l.cin * l.ntaps]
-        b = self.params[self.plan.param_base + l.b_off: self.plan.param_base + l.b_off + l.M]
-        return w.reshape(l.M, l.cin, l.ntaps), b
+        lo = self.plan.param_base + (l.b_off if bias else l.w_off)
+        n = l.M if bias else l.M * l.cin * l.ntaps
+        self._note("params", lo, lo + n, "r")
+        return self.params[lo:lo + n] if bias else self.params[lo:lo + n].reshape(l.M, l.cin, l.ntaps)
 
     # ---- ops ---------------------------------------------------------------------------------------------
     def run(self, ops):
         for op in ops:
+            if self.rec is not None:
+                self.rec.append(set())
             getattr(self, "op_" + op.type)(**op.a)
 
     def op_pack_input(self, src, dst, B, C, H, W, R, cpad):
-        x = self.t[src].reshape(B, C, H, W)
+        x = self.get(src).reshape(B, C, H, W)
         rots = [x]
         if R == 4:
             rots = [x, x.flip(3).transpose(2, 3), x.flip(3).flip(2), x.flip(2).transpose(2, 3)]
@@ -89,20 +119,20 @@ class Interp:
     def op_wpack(self, layer, M, cin, ntaps, c0, c1_real, Mpad_f, Ktot, Mpad_d, Kd, need_d, cm_f=False, cm_d=False):
         # (cm_f / cm_d: the device also writes chunk-major pre-swizzled copies for k_cdma -- a layout detail of the HIP library,
         #  checked through the convolutions that read them)
-        w, _ = self.weight(layer)                       # [M, cin, ntaps]
+        w = self.weight(layer)                          # [M, cin, ntaps]
         kmap = [k if k < c0 else (c0 + k - c0 if k - c0 < c1_real else -1) for k in range(Ktot)]
         wf = torch.zeros(ntaps, Mpad_f, Ktot)
         for k, ci in enumerate(kmap):
             if ci >= 0:
                 wf[:, :M, k] = w[:, ci, :].t()
-        self.t[self.plan.prefix + "wf/" + layer] = _r16(wf, self.fp16)
+        self.put(self.plan.prefix + "wf/" + layer, _r16(wf, self.fp16))
         if need_d:
             wd = torch.zeros(ntaps, Mpad_d, Kd)
             for c in range(min(Mpad_d, Ktot)):
                 ci = kmap[c]
                 if ci >= 0:
                     wd[:, c, :M] = w[:, ci, :].t()
-            self.t[self.plan.prefix + "wd/" + layer] = _r16(wd, self.fp16, "bf16")
+            self.put(self.plan.prefix + "wd/" + layer, _r16(wd, self.fp16, "bf16"))
 
     def _gather(self, src0, src1, c0, c1, up0, N, H, W):
         parts = []
@@ -132,17 +162,17 @@ class Interp:
                 ltw, lth, ltn, kc, bf16=0, kreal=0, pool=None, pool_shifted=0, upsum=None, upsum_mask=None, upsum_c=0,
                 unrot=None, unrot_mask=None, unrot_smask=None, urot=None, urot_smask=None, sign_out=None, mask_sign=None, upsum_mask_sign=None):
         x = self._gather(src0, src1, c0, c1, up0, N, H, W)
-        wp = self.t[self.plan.prefix + ("wf/" if role == "fwd" else "wd/") + layer]
+        wp = self.get(self.plan.prefix + ("wf/" if role == "fwd" else "wd/") + layer)
         assert wp.shape == (len(taps), Mpad, Ktot), (wp.shape, len(taps), Mpad, Ktot)
         out = torch.zeros(N, H, W, M)
         for t, (dy, dx) in enumerate(taps):
             out += torch.einsum("nhwk,mk->nhwm", self._shift(x, dy, dx), wp[t, :M])
         if bias:
-            out += self.weight(layer)[1]
+            out += self.weight(layer, bias=True)
         if act:
             out = torch.where(out > 0, out, LRELU * out)
         if dst32 is not None:
-            self.t[dst32] = out.permute(0, 3, 1, 2).contiguous()
+            self.put(dst32, out.permute(0, 3, 1, 2).contiguous())
             return
         if urot is not None:       # fused SSDN_OP_UNROT_FWD of the (rounded) output; nothing goes to dst
             self._unrot_fwd(_r16(out, self.fp16, self.plan.tensors[urot.t].kind), urot, N // 4, H, M, urot_smask)
@@ -150,7 +180,7 @@ class Interp:
         if add is not None:
             out = out + self.view(add, M)
         if mask_sign is not None:      # sign bytes of the tensor `mask` views (written by its producer: sign_out)
-            out = out * torch.where(_unpack_signs(self.t[mask_sign], M) > 0, 1.0, LRELU)
+            out = out * torch.where(_unpack_signs(self.get(mask_sign), M) > 0, 1.0, LRELU)
         elif mask is not None:
             out = out * _lgrad(self.view(mask, M))
         if unrot is not None:      # fused SSDN_OP_UNROT_BWD of the (rounded) output; nothing goes to dst
@@ -161,7 +191,7 @@ class Interp:
                 gs = self._rot(g[..., r * C4:(r + 1) * C4], ang)
                 outs.append(torch.cat([gs[:, 1:], torch.zeros(N, 1, W, C4)], 1))
             if unrot_smask is not None:      # the sign bytes SSDN_OP_UNROT_FWD left (rows y <= P-2; row P-1 only meets zeros)
-                lg = torch.where(_unpack_signs(self.t[unrot_smask], C4) > 0, 1.0, LRELU)
+                lg = torch.where(_unpack_signs(self.get(unrot_smask), C4) > 0, 1.0, LRELU)
             else:
                 lg = _lgrad(self.view(unrot_mask, C4))
             self.store(unrot, C4, torch.cat(outs, 0) * lg)
@@ -170,18 +200,19 @@ class Interp:
             r = _r16(out[..., :upsum_c], self.fp16, self.plan.tensors[dst.t].kind)
             sm = r.reshape(N, H // 2, 2, W // 2, 2, upsum_c).sum((2, 4))
             if upsum_mask_sign is not None:      # sign bytes of the tensor `upsum_mask` views (written by its producer: sign_out)
-                lg = torch.where(_unpack_signs(self.t[upsum_mask_sign], upsum_c) > 0, 1.0, LRELU)
+                lg = torch.where(_unpack_signs(self.get(upsum_mask_sign), upsum_c) > 0, 1.0, LRELU)
             else:
                 lg = _lgrad(self.view(upsum_mask, upsum_c))
             self.store(upsum, upsum_c, sm * lg)
             if M > upsum_c:
+                self._note(dst.t, dst.co + upsum_c, dst.co + M, "w")
                 self.alloc(dst.t)[..., dst.co + upsum_c:dst.co + M] = _r16(out[..., upsum_c:], self.fp16, self.plan.tensors[dst.t].kind)
             return
         self.store(dst, M, out)
         if sign_out is not None:
-            self.t[sign_out] = _pack_signs(self.view(dst, M))
+            self.put(sign_out, _pack_signs(self._own(dst, M)))
         if pool is not None:       # fused SSDN_OP_POOL_FWD of the stored (rounded) output
-            self.store(pool, M, self._windows(self.view(dst, M), pool_shifted).max(3).values)
+            self.store(pool, M, self._windows(self._own(dst, M), pool_shifted).max(3).values)
 
     def _windows(self, a, shifted):
         """[N,Ho,Wo,4,C] window values in scan order (row-major); the shifted variant sees a zero row on top."""
@@ -205,7 +236,7 @@ class Interp:
             nib = nib | ((mx > 0).to(torch.int64) << 3)
             sh = (4 * torch.arange(8, dtype=torch.int64)).repeat(C // 8)
             words = (nib << sh).reshape(N, H // 2, W // 2, C // 8, 8).sum(-1)
-            self.t[route] = words.to(torch.int64)
+            self.put(route, words.to(torch.int64))
 
     def op_pool_bwd(self, act, dpool, dz, N, H, W, C, shifted, route=None):
         a = self.view(act, C)
@@ -238,7 +269,7 @@ class Interp:
 
     def _unrot_fwd(self, y, dst, B, P, C, smask=None):
         if smask is not None:     # bit q of byte k = (channel 8k+q > 0)
-            self.t[smask] = _pack_signs(y)
+            self.put(smask, _pack_signs(y))
         s = torch.cat([torch.zeros(4 * B, 1, P, C), y[:, :-1]], 1)
         parts = [self._rot(s[r * B:(r + 1) * B], a) for r, a in enumerate((0, 270, 180, 90))]
         self.store(dst, 4 * C, torch.cat(parts, -1))
@@ -252,8 +283,9 @@ class Interp:
         self.store(dst, C, torch.cat(outs, 0) * _lgrad(self.view(mask, C)))
 
     def op_grad_pack(self, g, dst, N, C, H, W, cpad):
-        gg = self.t[g].reshape(N, C, H, W)
+        gg = self.get(g).reshape(N, C, H, W)
         self.scale = 1.0                       # bf16 gradients: no loss scaling
+        self._note(self.plan.prefix + "scale", 0, self.WHOLE, "w")      # (the device's scale word: SSDN_OP_WREDUCE's inv_scale input)
         out = torch.zeros(N, H, W, cpad)
         out[..., :C] = gg.permute(0, 2, 3, 1)
         self.store(dst, cpad, out)
@@ -262,7 +294,10 @@ class Interp:
                  slab=None, bslab=None, csplit=0, mblocks=1, kreal=0, mega=0, cost=0.0, **_planner_private):
         x = _r16(self._gather(src0, src1, c0, c1, up0, N, H, W), self.fp16, "bf16")   # staged as bf16 on the device
         self.slabs[slab], self.bslabs[bslab] = [], []
+        self._note(slab, 0, mblocks, "w")
+        self._note(bslab, 0, mblocks, "w")
         for mb in range(mblocks):        # a merged launch covers mblocks blocks of M output channels of the dz view
+            self._note(dz.t, dz.co + mb * M, dz.co + mb * M + M, "r")
             g = self.t[dz.t][..., dz.co + mb * M:dz.co + mb * M + M]
             sl = torch.zeros(len(taps), Mpad, Kpad)
             for t, (dy, dx) in enumerate(taps):
@@ -275,15 +310,22 @@ class Interp:
 
     def op_wreduce(self, layer, nslabs, ntaps, M, Mpad, Kpad, cin, cin_full, m_off, c_off, with_bias, tapblock=0,
                    slab=None, bslab=None, mblock=0):
-        sl, bsl = self.slabs[slab][mblock], self.bslabs[bslab][mblock]
+        sl = self.slabs[slab][mblock]
+        self._note(slab, mblock, mblock + 1, "r")
+        self._note(self.plan.prefix + "scale", 0, self.WHOLE, "r")
         l = self.L[layer]
         base = self.plan.param_base
         gw = self.grads[base + l.w_off: base + l.w_off + l.M * l.cin * l.ntaps].reshape(l.M, l.cin, l.ntaps)
         assert cin_full == l.cin
+        for m in range(m_off, m_off + M):      # (the rows of gw this block covers)
+            lo = base + l.w_off + (m * l.cin + c_off) * l.ntaps
+            self._note("grads", lo, lo + cin * l.ntaps, "w")
         if tapblock:     # the slab's taps are channel blocks of a 1x1 layer
             blk = sl[:, :M, :].permute(1, 0, 2).reshape(M, ntaps * Kpad)[:, :cin]
             gw[m_off:m_off + M, c_off:c_off + cin, 0] = blk / self.scale
         else:
             gw[m_off:m_off + M, c_off:c_off + cin, :] = sl[:, :M, :cin].permute(1, 2, 0) / self.scale
         if with_bias:
-            self.grads[base + l.b_off + m_off: base + l.b_off + m_off + M] = bsl[:M] / self.scale
+            self._note(bslab, mblock, mblock + 1, "r")
+            self._note("grads", base + l.b_off + m_off, base + l.b_off + m_off + M, "w")
+            self.grads[base + l.b_off + m_off: base + l.b_off + m_off + M] = self.bslabs[bslab][mblock][:M] / self.scale
