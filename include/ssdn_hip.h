@@ -718,6 +718,14 @@ int ssdn_wgrad_mega_ok(const ssdn_wgrad_args* a);
 /* The kernel variant the library runs the op with: out9 = {thin, MT, CPW, NL, BOTH, PS, KS, RWX, RWD}; returns the id of its
  * instance inside the chip-wide launch (>= 0), -1 if there is none, < -1 on invalid arguments.  (planner / test aid) */
 int ssdn_wgrad_variant(const ssdn_wgrad_args* a, int32_t* out9);
+/* The work split k_cdma (csrc/conv_dma.hip) would walk SSDN_OP_CONV with these arguments in: out8 = {tiles_x, tiles_y, segs, tps, nitems,
+ * grid, xcd_map, mt_blocks} -- 16x16 tiles per image; a strip (image, tile column) is cut into `segs` work items of `tps` consecutive tiles;
+ * `nitems` items on `grid` persistent workgroups (nitems > grid: workgroups take further items); xcd_map 1: each XCD walks a contiguous
+ * eighth of the items, 0: item = workgroup + k * grid; mt_blocks launches, one per block of up to 96 output channels.  Computed by the
+ * host code the launch itself uses, for the current device's compute units (256 without a device).  Returns 1 if the launch runs k_cdma
+ * under the current ssdn_conv_set_mode, 0 if another kernel serves it (out8 is then what k_cdma would have done), < 0 on invalid
+ * arguments.  (planner / test aid) */
+int ssdn_conv_dma_split(const ssdn_conv_args* a, int32_t* out8);
 
 /* sizeof() of the args struct for an op type (0: ssdn_op itself); lets a binding verify its struct mirrors */
 int ssdn_struct_size(int op_type);

@@ -180,6 +180,7 @@ bool conv_fuses_unrot(const ssdn_conv_args* a);                // conv_mfma.hip:
 bool conv_fuses_upsum(const ssdn_conv_args* a);                // conv_mfma.hip: k_cdma or the flat path applies the fused UPSUM_BWD
 bool conv_fuses_pool(const ssdn_conv_args* a);                  // conv_mfma.hip: the launch takes the flat path (fused max-pool)
 int launch_conv_dma(const ssdn_conv_args* a, hipStream_t s);
+void conv_dma_split(const ssdn_conv_args* a, int32_t* out8);    // conv_dma.hip: the work split launch_conv_dma gives the launch (ssdn_conv_dma_split)
 // conv16.hip: the 96-channel 3x3 layers at 16x16 pixels on a resident half-image tile (k_conv16)
 bool conv16_shape_ok(const ssdn_conv_args* a);                 // the kernel's shape class and epilogue flags (host code only)
 bool conv_use_conv16(const ssdn_conv_args* a);                 // conv_mfma.hip: launch_conv runs `a` on k_conv16

@@ -981,6 +981,37 @@ bool conv_dma_signs(const ssdn_conv_args* a) {
 
 int conv_dma_lds_bytes(int mt) { return 2 * CD_TBYTES + 2 * mt * 32 * 96; }
 
+// The work split of one k_cdma launch on `cus` compute units: the one place that decides it (cd_launch_kind launches what this says,
+// ssdn_conv_dma_split reports it).  Returns the grid; sets segs, tps, segs_sh, tx_magic, nitems, xcd_map of x (tiles_x / tiles_y are set).
+static int cd_split(int N, int cus, CdAux& x) {
+    // cut the strips into segments until there are two work items per CU (or one tile per item)
+    const int nstrips = N * x.tiles_x;
+    x.segs = 1;
+    while (nstrips * x.segs < 2 * cus && x.segs < x.tiles_y && x.tiles_y % (x.segs * 2) == 0) x.segs *= 2;
+    x.tps = x.tiles_y / x.segs;
+    x.segs_sh = 0;
+    while ((1 << x.segs_sh) < x.segs) ++x.segs_sh;
+    x.tx_magic = x.tiles_x > 1 ? (unsigned)((0x100000000ull + x.tiles_x - 1) / x.tiles_x) : 0u;
+    x.nitems = nstrips * x.segs;
+    const int grid = x.nitems < 2 * cus ? x.nitems : 2 * cus;
+    x.xcd_map = (x.nitems % 8 == 0 && grid % 8 == 0) ? 1 : 0;
+    return grid;
+}
+
+// out8 = {tiles_x, tiles_y, segs, tps, nitems, grid, xcd_map, mt_blocks} of the launch(es) launch_conv_dma would make (one per block of
+// up to 96 output channels, all with the same split); without a device: 256 CUs, as conv_dma_eligible assumes
+void conv_dma_split(const ssdn_conv_args* a, int32_t* out8) {
+    CdAux x;
+    x.tiles_x = a->W >> 4; x.tiles_y = a->H >> 4;
+    int cus = ssdn_device_cus();
+    if (cus <= 0) cus = 256;
+    const int grid = cd_split(a->N, cus, x);
+    int blocks = 0;
+    for (int mb = 0; mb < a->Mpad && a->M - mb > 0; mb += 96) ++blocks;
+    out8[0] = x.tiles_x; out8[1] = x.tiles_y; out8[2] = x.segs; out8[3] = x.tps;
+    out8[4] = x.nitems; out8[5] = grid; out8[6] = x.xcd_map; out8[7] = blocks;
+}
+
 template <int MT, bool BF, int EPI, int KIND>
 static int cd_launch_kind(const ssdn_conv_args* a, CdAux x, hipStream_t s) {
     static bool attr_set_dev[SSDN_MAX_DEVICES_ATTR] = {};
@@ -991,17 +1022,7 @@ static int cd_launch_kind(const ssdn_conv_args* a, CdAux x, hipStream_t s) {
     }
     int cus = ssdn_device_cus();
     if (cus <= 0) return -1;
-    // cut the strips into segments until there are two work items per CU (or one tile per item)
-    const int nstrips = a->N * x.tiles_x;
-    x.segs = 1;
-    while (nstrips * x.segs < 2 * cus && x.segs < x.tiles_y && x.tiles_y % (x.segs * 2) == 0) x.segs *= 2;
-    x.tps = x.tiles_y / x.segs;
-    x.segs_sh = 0;
-    while ((1 << x.segs_sh) < x.segs) ++x.segs_sh;
-    x.tx_magic = x.tiles_x > 1 ? (unsigned)((0x100000000ull + x.tiles_x - 1) / x.tiles_x) : 0u;
-    x.nitems = nstrips * x.segs;
-    const int grid = x.nitems < 2 * cus ? x.nitems : 2 * cus;
-    x.xcd_map = (x.nitems % 8 == 0 && grid % 8 == 0) ? 1 : 0;
+    const int grid = cd_split(a->N, cus, x);
     const double px = (double)a->N * a->H * a->W;
     const int kreal = a->kreal > 0 ? a->kreal : a->Ktot;
     const double flops = 2.0 * px * x.m_cnt * kreal * 9;

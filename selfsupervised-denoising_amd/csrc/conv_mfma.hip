@@ -947,6 +947,14 @@ bool conv_fuses_upsum(const ssdn_conv_args* a) {
     return conv_flat_path(a);
 }
 
+extern "C" int ssdn_conv_dma_split(const ssdn_conv_args* a, int32_t* out8) {
+    if (!a || !out8) return ssdn_set_error("conv_dma_split: null argument");
+    const int rc = conv_validate(a);
+    if (rc) return rc;
+    conv_dma_split(a, out8);
+    return !conv_use_gemm(a) && !conv_use_thin(a) && conv_use_dma(a) ? 1 : 0;      // launch_conv's order
+}
+
 int launch_conv(const ssdn_conv_args* a, hipStream_t s) {
     int rc = conv_validate(a);
     if (rc) return rc;
