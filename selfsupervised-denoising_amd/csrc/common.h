@@ -162,6 +162,9 @@ int launch_metrics(const ssdn_metrics_args* a, hipStream_t s);
 int launch_accum(const ssdn_accum_args* a, hipStream_t s);
 int launch_noise(const ssdn_noise_args* a, hipStream_t s);
 int launch_input_grad(const ssdn_input_grad_args* a, hipStream_t s);   // input_grad.hip
+// conv_mfma.hip::conv_route decides which of its five kernels serves an SSDN_OP_CONV; launch_conv and the conv_* queries
+// (conv_lds_bytes, conv_signs, conv_fuses_*, conv_use_conv16, conv_*_fusable) read that one decision.  The per-kernel shape classes
+// (gemm_dma_eligible, conv_thin_eligible, conv_dma_eligible, conv16_shape_ok) and capability tests stay with their kernels.
 int conv_lds_bytes(const ssdn_conv_args* a);
 int conv_validate(const ssdn_conv_args* a);                     // conv_mfma.hip: argument checks shared by every conv launcher
 // conv_chain.hip: a run of consecutive main-lane ops on images of <= 64 pixels (3x3 forward layers; data gradients + SSDN_OP_POOL_BWD)
@@ -183,24 +186,30 @@ int launch_conv_dma(const ssdn_conv_args* a, hipStream_t s);
 void conv_dma_split(const ssdn_conv_args* a, int32_t* out8);    // conv_dma.hip: the work split launch_conv_dma gives the launch (ssdn_conv_dma_split)
 // conv16.hip: the 96-channel 3x3 layers at 16x16 pixels on a resident half-image tile (k_conv16)
 bool conv16_shape_ok(const ssdn_conv_args* a);                 // the kernel's shape class and epilogue flags (host code only)
-bool conv_use_conv16(const ssdn_conv_args* a);                 // conv_mfma.hip: launch_conv runs `a` on k_conv16
+bool conv_use_conv16(const ssdn_conv_args* a);                 // conv_mfma.hip: `a` runs on k_conv16 (ssdn_conv16_eligible)
 int conv16_lds_bytes(const ssdn_conv_args* a);
 int launch_conv16(const ssdn_conv_args* a, hipStream_t s);
 // conv_thin.hip: forward 3x3 layer with 1..3 real input channels (encode_block_1.0) as an im2col-shaped GEMM
 bool conv_thin_eligible(const ssdn_conv_args* a);
-bool conv_thin_fuses_pack(const ssdn_pack_input_args* pk, const ssdn_conv_args* a);   // (the conv must still pass launch_conv's own routing)
+bool conv_thin_fuses_pack(const ssdn_pack_input_args* pk, const ssdn_conv_args* a);   // (the kernel's own test: conv_pack_fusable asks the route too)
 int launch_conv_thin(const ssdn_conv_args* a, const ssdn_pack_input_args* pk, hipStream_t s);
-bool conv_pack_fusable(const ssdn_pack_input_args* pk, const ssdn_conv_args* a);      // conv_mfma.hip: launch_conv would route `a` to k_conv_thin
+bool conv_pack_fusable(const ssdn_pack_input_args* pk, const ssdn_conv_args* a);      // conv_mfma.hip: `a` runs on k_conv_thin and the pack folds into it
 // gradpack_dgrad.hip: SSDN_OP_GRAD_PACK + the data gradient of the narrow net_out layer behind it as one launch
 bool gradpack_dgrad_fusable(const ssdn_grad_pack_args* gp, const ssdn_conv_args* a);
 int launch_gradpack_dgrad(const ssdn_grad_pack_args* gp, const ssdn_conv_args* a, hipStream_t s);
-bool conv_gradpack_fusable(const ssdn_grad_pack_args* gp, const ssdn_conv_args* a);   // conv_mfma.hip: ... and launch_conv would run `a` as plain k_conv
+bool conv_gradpack_fusable(const ssdn_grad_pack_args* gp, const ssdn_conv_args* a);   // conv_mfma.hip: ... and `a` runs on k_conv
 // gemm_dma.hip: 1x1 layers with 96 / 384 output channels as a one-pass LDS-DMA GEMM
 bool gemm_dma_eligible(const ssdn_conv_args* a);
 int gemm_dma_lds_bytes(const ssdn_conv_args* a);
 int launch_gemm_dma(const ssdn_conv_args* a, hipStream_t s);
 bool gemm_dma_fuses_next(const ssdn_conv_args* a, const ssdn_conv_args* b);   // the narrow 1x1 layer b behind the 96-channel 1x1 layer a: one launch
 int launch_gemm_dma_with_next(const ssdn_conv_args* a, const ssdn_conv_args* b, hipStream_t s);
-bool conv_pair_fusable(const ssdn_conv_args* a, const ssdn_conv_args* b);     // conv_mfma.hip: launch_conv would route `a` to k_gdma and b can ride along
+bool conv_pair_fusable(const ssdn_conv_args* a, const ssdn_conv_args* b);     // conv_mfma.hip: `a` runs on k_gdma and b can ride along
 extern "C" int ssdn_device_cus(void);
+// the device's compute units for host-side sizing rules; without a device (planning on a CPU-only host) those of an MI355X
+#define SSDN_CUS_NO_DEVICE 256
+static inline int ssdn_cus_or_default() {
+    const int cus = ssdn_device_cus();
+    return cus > 0 ? cus : SSDN_CUS_NO_DEVICE;
+}
 int wgrad_lds_bytes(const ssdn_wgrad_args* a);

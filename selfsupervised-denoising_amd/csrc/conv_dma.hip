@@ -954,8 +954,7 @@ bool conv_dma_eligible(const ssdn_conv_args* a, bool any_size) {
     // worth it from one 256-pixel tile per CU upwards, and from one per TWO CUs where an image is more than one tile (round 6: the plain
     // network's 32x32 stage at batch 32; not the blind-spot network's 16x16 stage, which runs beside the half-chip weight-gradient launch:
     // ssdn/hip/graph.py::cdma_fills mirrors the rule and says what was measured)
-    int cus = ssdn_device_cus();
-    if (cus <= 0) cus = 256;
+    const int cus = ssdn_cus_or_default();
     const long long tiles = (long long)a->N * (a->H >> 4) * (a->W >> 4);
     if (!(tiles >= cus || (2 * tiles >= cus && a->H * a->W > 256)) && !any_size) return false;
     if ((long long)a->N * (a->W >> 4) >= 65536) return false;    // (strips: the tile walk's reciprocal multiply, CdAux.tx_magic)
@@ -1003,9 +1002,7 @@ static int cd_split(int N, int cus, CdAux& x) {
 void conv_dma_split(const ssdn_conv_args* a, int32_t* out8) {
     CdAux x;
     x.tiles_x = a->W >> 4; x.tiles_y = a->H >> 4;
-    int cus = ssdn_device_cus();
-    if (cus <= 0) cus = 256;
-    const int grid = cd_split(a->N, cus, x);
+    const int grid = cd_split(a->N, ssdn_cus_or_default(), x);
     int blocks = 0;
     for (int mb = 0; mb < a->Mpad && a->M - mb > 0; mb += 96) ++blocks;
     out8[0] = x.tiles_x; out8[1] = x.tiles_y; out8[2] = x.segs; out8[3] = x.tps;

@@ -767,10 +767,22 @@ static bool conv_uses_mt1(const ssdn_conv_args* a, const ConvGeom& g) {
     static int mt1_tiles = -1;
     if (mt1_tiles < 0) {
         const char* e = ssdn_tuning_env("SSDN_CONV_MT1_TILES");       // tuning override
-        mt1_tiles = e ? atoi(e) : ssdn_device_cus();
-        if (mt1_tiles <= 0) mt1_tiles = 256;                  // no device (planning on a CPU-only host)
+        mt1_tiles = e ? atoi(e) : ssdn_cus_or_default();
+        if (mt1_tiles <= 0) mt1_tiles = SSDN_CUS_NO_DEVICE;
     }
     return !a->dst32 && g.tiles_x * g.tiles_y * g.groups_n <= mt1_tiles && a->Mpad >= 64;
+}
+
+// ALLW (-> *allw) and FLAT (returned; see k_conv) of a k_conv launch in blocks of mt x 32 output channels.  FLAT: ALLW + the 256-pixel
+// tile is made of whole images.  The two A/B knobs are read here, once, and nowhere else.
+static int conv_staging(const ssdn_conv_args* a, const ConvGeom& g, int mt, int* allw) {
+    static const bool no_allw = ssdn_tuning_env("SSDN_CONV_NO_ALLW") != nullptr;
+    static const bool no_flat = ssdn_tuning_env("SSDN_CONV_NO_FLAT") != nullptr;
+    const int ks = a->kc / 16, threads = a->ltw + a->lth + a->ltn > 8 ? 512 : 256;      // (the instantiation conv_launch_ks picks)
+    const int m_last = a->M - (a->Mpad - 32);                                // real channels of the last 32-channel block
+    *allw = (!no_allw && conv_allw(*a, g, mt, a->kc) && !conv_async(*a, a->kc)) ? 1 : 0;
+    return (*allw && !no_flat && threads == 256 && ks <= 4 && g.TW == a->W && g.TH == a->H && g.TN * g.TH * g.TW == 256 && a->N % g.TN == 0 &&
+            (m_last == 32 || m_last == 16 || m_last == 8) && (!a->up0 || !((a->H | a->W) & 1))) ? 1 : 0;
 }
 
 // which kernel serves a layer: 0 = always k_conv, 1 = k_cdma where its shape class fits AND the layer has >= 1 tile per CU
@@ -782,11 +794,6 @@ extern "C" int ssdn_conv_set_mode(int mode) {
     g_conv_mode = mode;
     return 0;
 }
-// (a launch that must write the fused max-pool output takes k_conv's flat path)
-static bool conv_use_dma(const ssdn_conv_args* a) { return g_conv_mode > 0 && !a->pool.p && conv_dma_eligible(a, g_conv_mode == 2); }
-static bool conv_use_gemm(const ssdn_conv_args* a) { return g_conv_mode > 0 && gemm_dma_eligible(a); }
-static bool conv_use_thin(const ssdn_conv_args* a) { return g_conv_mode > 0 && conv_thin_eligible(a); }
-static bool conv_flat_path(const ssdn_conv_args* a);
 // k_conv16 (conv16.hip) takes, of the launches that would run k_conv's flat path, the 96-channel layers at 16x16 pixels; bit 0 of the
 // roles: forward, bit 1: data gradient (ssdn_conv_set_conv16: 0 leaves every launch where it was -- test and A/B aid; -1: the default).
 // Default: the data gradient only.  Forward measured no faster than k_conv (profiles/conv16_ab.txt: both stream the whole weight tensor
@@ -798,19 +805,49 @@ extern "C" int ssdn_conv_set_conv16(int roles) {
     g_conv16_roles = roles < 0 ? CONV16_DEFAULT_ROLES : roles;
     return 0;
 }
-bool conv_use_conv16(const ssdn_conv_args* a) {
-    return g_conv_mode > 0 && (g_conv16_roles & (a->bf16 ? 2 : 1)) && !conv_validate(a) && conv16_shape_ok(a) && !conv_use_gemm(a) &&
-           !conv_use_thin(a) && !conv_use_dma(a) && conv_flat_path(a);
+
+// The kernel of an SSDN_OP_CONV.  conv_route is the ONE place that decides it -- the order of the five kernels, the mode, the k_conv16 roles,
+// the fused max-pool's claim on k_conv -- from the kernels' own shape classes; launch_conv and every query read the route.  < 0: conv_validate's error.
+enum ConvKernel { CONV_K_GDMA, CONV_K_THIN, CONV_K_CDMA, CONV_K_CONV16, CONV_K_CONV };
+// geom, mt1, flat (CONV_K_CONV16 / CONV_K_CONV only): k_conv's tiling, whether it runs as 32-channel blocks, and those on the flat path
+struct ConvRoute { ConvKernel kernel; ConvGeom geom; bool mt1, flat; };
+static int conv_route(const ssdn_conv_args* a, ConvRoute* r) {
+    const int rc = conv_validate(a);
+    if (rc) return rc;
+    const bool dma_kernels = g_conv_mode > 0;                  // mode 0: k_conv always
+    if (dma_kernels && gemm_dma_eligible(a)) { r->kernel = CONV_K_GDMA; return 0; }
+    if (dma_kernels && conv_thin_eligible(a)) { r->kernel = CONV_K_THIN; return 0; }
+    // (a launch that must write the fused max-pool output takes k_conv's flat path)
+    if (dma_kernels && !a->pool.p && conv_dma_eligible(a, g_conv_mode == 2)) { r->kernel = CONV_K_CDMA; return 0; }
+    r->geom = conv_geom(a->ltw, a->lth, a->ltn, a->ntaps, a->dy, a->dx, a->N, a->H, a->W, a->kc);
+    r->mt1 = conv_uses_mt1(a, r->geom);
+    int allw;
+    r->flat = conv_staging(a, r->geom, 1, &allw) && r->mt1;
+    r->kernel = dma_kernels && (g_conv16_roles & (a->bf16 ? 2 : 1)) && conv16_shape_ok(a) && r->flat ? CONV_K_CONV16 : CONV_K_CONV;
+    return 0;
 }
-bool conv_gradpack_fusable(const ssdn_grad_pack_args* gp, const ssdn_conv_args* a) {
-    return !conv_validate(a) && !conv_use_gemm(a) && !conv_use_thin(a) && !conv_use_dma(a) && gradpack_dgrad_fusable(gp, a);
+
+static bool conv_routed_to(const ssdn_conv_args* a, ConvKernel k) { ConvRoute r; return !conv_route(a, &r) && r.kernel == k; }
+
+// What the route's kernel can do for the launch: the owning kernel's capability test (launch_conv refuses what these refuse)
+static bool route_signs(const ssdn_conv_args* a, const ConvRoute& r) {
+    if (r.kernel == CONV_K_GDMA) return !a->upsum_mask_sign && gemm_dma_signs(a);
+    if (r.kernel == CONV_K_THIN) return a->sign_out && !a->mask_sign && !a->upsum_mask_sign;       // k_conv_thin writes them (forward only)
+    // (conv_dma_signs asks for k_cdma's default size rule even in mode 2: 0 at fixture sizes there, although k_cdma runs the launch)
+    return r.kernel == CONV_K_CDMA && conv_dma_signs(a);
 }
-bool conv_pair_fusable(const ssdn_conv_args* a, const ssdn_conv_args* b) {
-    return !conv_validate(a) && !conv_validate(b) && conv_use_gemm(a) && gemm_dma_fuses_next(a, b);
+static bool route_fuses_upsum(const ssdn_conv_args* a, const ConvRoute& r) {
+    if (!a->bf16 || a->dst32 || a->mask.p || a->add.p || (a->H & 1) || (a->W & 1)) return false;
+    if ((a->upsum_c & 7) || a->upsum_c > a->M || a->upsum_c <= 0) return false;
+    if (r.kernel == CONV_K_CDMA) return a->upsum_c % 96 == 0;
+    return (r.kernel == CONV_K_CONV16 || r.kernel == CONV_K_CONV) && r.flat;
 }
-bool conv_pack_fusable(const ssdn_pack_input_args* pk, const ssdn_conv_args* a) {
-    return !conv_validate(a) && !conv_use_gemm(a) && conv_use_thin(a) && conv_thin_fuses_pack(pk, a);
-}
+static bool route_fuses_pool(const ssdn_conv_args* a, const ConvRoute& r) { return !a->bf16 && !a->dst32 && a->act && !(a->H & 1) && !(a->W & 1) && r.kernel == CONV_K_CONV && r.flat; }
+bool conv_use_conv16(const ssdn_conv_args* a) { return conv_routed_to(a, CONV_K_CONV16); }
+// (the executor asks these in front of every conv op: the kernel's own test, which refuses nearly all of them, comes before the route)
+bool conv_gradpack_fusable(const ssdn_grad_pack_args* gp, const ssdn_conv_args* a) { return gradpack_dgrad_fusable(gp, a) && conv_routed_to(a, CONV_K_CONV); }
+bool conv_pair_fusable(const ssdn_conv_args* a, const ssdn_conv_args* b) { return gemm_dma_fuses_next(a, b) && conv_routed_to(a, CONV_K_GDMA) && !conv_validate(b); }
+bool conv_pack_fusable(const ssdn_pack_input_args* pk, const ssdn_conv_args* a) { return conv_thin_fuses_pack(pk, a) && conv_routed_to(a, CONV_K_THIN); }
 
 int conv_validate(const ssdn_conv_args* a) {
     if (a->ntaps < 1 || a->ntaps > SSDN_MAX_TAPS) return ssdn_set_error("conv: ntaps out of range");
@@ -838,25 +875,15 @@ static size_t conv_lds(const ssdn_conv_args* a, const ConvGeom& g, int mt) {
 }
 
 int conv_lds_bytes(const ssdn_conv_args* a) {
-    if (conv_validate(a)) return -1;
-    if (conv_use_gemm(a)) return gemm_dma_lds_bytes(a);
-    if (conv_use_thin(a)) return 32 * 1024;                     // (halo of four channel slots + four wave-private transpose tiles: < 32 KB)
-    if (conv_use_dma(a)) return conv_dma_lds_bytes(a->Mpad >= 96 ? 3 : a->Mpad / 32);
-    if (conv_use_conv16(a)) return conv16_lds_bytes(a);
-    ConvGeom g = conv_geom(a->ltw, a->lth, a->ltn, a->ntaps, a->dy, a->dx, a->N, a->H, a->W, a->kc);
-    int mt = a->Mpad / 32;
-    if (mt > 3) mt = 3;
-    if (conv_uses_mt1(a, g)) mt = 1;
-    else if (a->kc == 96) { ssdn_set_error("conv: kc = 96 is only built for layers that run as 32-channel blocks (<= 1 tile per CU)"); return -1; }
-    return (int)conv_lds(a, g, mt);
-}
-
-// FLAT: ALLW + the 256-pixel tile is made of whole images (see k_conv)
-static bool conv_flat_ok(const ssdn_conv_args* a, const ConvGeom& g, int ks, int threads) {
-    static const bool no_flat = ssdn_tuning_env("SSDN_CONV_NO_FLAT") != nullptr;      // A/B aid, read once
-    const int m_last = a->M - (a->Mpad - 32);                                // real channels of the last 32-channel block
-    return !no_flat && threads == 256 && ks <= 4 && g.TW == a->W && g.TH == a->H && g.TN * g.TH * g.TW == 256 && a->N % g.TN == 0 &&
-           (m_last == 32 || m_last == 16 || m_last == 8) && (!a->up0 || !((a->H | a->W) & 1));
+    ConvRoute r;
+    if (conv_route(a, &r)) return -1;
+    if (r.kernel == CONV_K_GDMA) return gemm_dma_lds_bytes(a);
+    if (r.kernel == CONV_K_THIN) return 32 * 1024;              // (halo of four channel slots + four wave-private transpose tiles: < 32 KB)
+    if (r.kernel == CONV_K_CDMA) return conv_dma_lds_bytes(a->Mpad >= 96 ? 3 : a->Mpad / 32);
+    if (r.kernel == CONV_K_CONV16) return conv16_lds_bytes(a);
+    // (launch_conv has its own text for this, "unsupported kc", from conv_launch_ks)
+    if (!r.mt1 && a->kc == 96) { ssdn_set_error("conv: kc = 96 is only built for layers that run as 32-channel blocks (<= 1 tile per CU)"); return -1; }
+    return (int)conv_lds(a, r.geom, r.mt1 ? 1 : a->Mpad / 32 > 3 ? 3 : a->Mpad / 32);
 }
 
 template <int MT, bool BF, int KS, int CONV_THREADS>
@@ -880,9 +907,7 @@ static int conv_launch_mt(const ssdn_conv_args* a, const ConvGeom& g, ConvAux x,
     double bytes = px * (a->c0 * 2.0 / (a->up0 ? 4.0 : 1.0) + a->c1 * 2.0) + px * m_real * (a->dst32 ? 4.0 : 2.0);
     prof_begin(3 - MT, s);
     x.nblk = nblk_y;
-    static const bool no_allw = ssdn_tuning_env("SSDN_CONV_NO_ALLW") != nullptr;      // A/B aid, read once
-    x.allw = (!no_allw && conv_allw(*a, g, MT, a->kc) && !conv_async(*a, a->kc)) ? 1 : 0;
-    x.flat = (x.allw && conv_flat_ok(a, g, KS, CONV_THREADS)) ? 1 : 0;
+    x.flat = conv_staging(a, g, MT, &x.allw);
     if (a->pool.p && !x.flat) return ssdn_set_error("conv: fused max-pool requested for a launch that does not take the flat path");
     if (a->upsum.p && !x.flat) return ssdn_set_error("conv: fused upsum requested for a launch that does not take the flat path");
     const int grid_all = nblk_y > 1 ? ((grid + 7) / 8) * 8 * nblk_y : grid;
@@ -906,68 +931,48 @@ static int conv_launch_ks(const ssdn_conv_args* a, const ConvGeom& g, ConvAux x,
     return ssdn_set_error("conv: unsupported kc %d", a->kc);
 }
 
-
-bool conv_fuses_pool(const ssdn_conv_args* a) {
-    static const bool no_allw = ssdn_tuning_env("SSDN_CONV_NO_ALLW") != nullptr;
-    if (conv_validate(a) || a->bf16 || a->dst32 || !a->act || (a->H & 1) || (a->W & 1)) return false;
-    if (conv_use_gemm(a)) return false;
-    ConvGeom g = conv_geom(a->ltw, a->lth, a->ltn, a->ntaps, a->dy, a->dx, a->N, a->H, a->W, a->kc);
-    const bool wide = a->ltw + a->lth + a->ltn > 8;
-    return conv_uses_mt1(a, g) && !no_allw && conv_allw(*a, g, 1, a->kc) && !conv_async(*a, a->kc) &&
-           conv_flat_ok(a, g, a->kc / 16, wide ? 512 : 256);
-}
-
-static bool conv_flat_path(const ssdn_conv_args* a) {
-    static const bool no_allw = ssdn_tuning_env("SSDN_CONV_NO_ALLW") != nullptr;
-    ConvGeom g = conv_geom(a->ltw, a->lth, a->ltn, a->ntaps, a->dy, a->dx, a->N, a->H, a->W, a->kc);
-    const bool wide = a->ltw + a->lth + a->ltn > 8;
-    return conv_uses_mt1(a, g) && !no_allw && conv_allw(*a, g, 1, a->kc) && !conv_async(*a, a->kc) &&
-           conv_flat_ok(a, g, a->kc / 16, wide ? 512 : 256);
-}
-bool conv_signs(const ssdn_conv_args* a) {
-    if (!(a->sign_out || a->mask_sign || a->upsum_mask_sign) || conv_validate(a)) return false;
-    if (conv_use_gemm(a)) return !a->upsum_mask_sign && gemm_dma_signs(a);
-    if (conv_use_thin(a)) return a->sign_out && !a->mask_sign && !a->upsum_mask_sign;       // k_conv_thin writes them (forward only)
-    return conv_use_dma(a) && conv_dma_signs(a);
-}
-bool conv_fuses_urot(const ssdn_conv_args* a) {
-    return a->urot.p && !conv_validate(a) && !conv_use_gemm(a) && !conv_use_thin(a) && conv_use_dma(a);   // (conv_dma_eligible checks the shape)
-}
+// The exported queries: each a read of the route
+bool conv_signs(const ssdn_conv_args* a) { ConvRoute r; return (a->sign_out || a->mask_sign || a->upsum_mask_sign) && !conv_route(a, &r) && route_signs(a, r); }
+bool conv_fuses_urot(const ssdn_conv_args* a) { return a->urot.p && conv_routed_to(a, CONV_K_CDMA); }      // (conv_dma_eligible checks the shape)
 bool conv_fuses_unrot(const ssdn_conv_args* a) {
-    // (the query is about the launch WITH the fused output requested)
-    ssdn_conv_args q = *a;
+    ssdn_conv_args q = *a;      // (the query is about the launch WITH the fused output requested: the caller may have left it empty)
     if (!q.unrot.p) { q.unrot = q.dst; q.unrot_mask = q.dst; }
-    return !conv_validate(&q) && conv_use_gemm(&q);
+    return conv_routed_to(&q, CONV_K_GDMA);
 }
-bool conv_fuses_upsum(const ssdn_conv_args* a) {
-    if (conv_validate(a) || !a->bf16 || a->dst32 || a->mask.p || a->add.p || (a->H & 1) || (a->W & 1)) return false;
-    if ((a->upsum_c & 7) || a->upsum_c > a->M || a->upsum_c <= 0) return false;
-    if (conv_use_gemm(a)) return false;
-    if (conv_use_dma(a)) return a->upsum_c % 96 == 0;
-    return conv_flat_path(a);
+bool conv_fuses_upsum(const ssdn_conv_args* a) { ConvRoute r; return !conv_route(a, &r) && route_fuses_upsum(a, r); }
+bool conv_fuses_pool(const ssdn_conv_args* a) {
+    ssdn_conv_args q = *a;      // (likewise WITH the pooled output requested, which keeps the launch off k_conv_thin, k_cdma and k_conv16)
+    if (!q.pool.p) q.pool = q.dst;
+    ConvRoute r;
+    return !conv_route(&q, &r) && route_fuses_pool(&q, r);
 }
 
 extern "C" int ssdn_conv_dma_split(const ssdn_conv_args* a, int32_t* out8) {
     if (!a || !out8) return ssdn_set_error("conv_dma_split: null argument");
-    const int rc = conv_validate(a);
+    ConvRoute r;
+    const int rc = conv_route(a, &r);
     if (rc) return rc;
     conv_dma_split(a, out8);
-    return !conv_use_gemm(a) && !conv_use_thin(a) && conv_use_dma(a) ? 1 : 0;      // launch_conv's order
+    return r.kernel == CONV_K_CDMA ? 1 : 0;
 }
 
 int launch_conv(const ssdn_conv_args* a, hipStream_t s) {
-    int rc = conv_validate(a);
+    ConvRoute r;
+    int rc = conv_route(a, &r);
     if (rc) return rc;
-    if ((a->sign_out || a->mask_sign || a->upsum_mask_sign) && !conv_signs(a)) return ssdn_set_error("conv: sign bytes requested for a launch that cannot write / read them (ssdn_conv_signs)");
-    if (a->urot.p && !conv_fuses_urot(a)) return ssdn_set_error("conv: fused UNROT_FWD requested for a launch that cannot fuse it (ssdn_conv_fuses_urot)");
-    if (a->unrot.p && !conv_fuses_unrot(a)) return ssdn_set_error("conv: fused UNROT_BWD requested for a launch that cannot fuse it (ssdn_conv_fuses_unrot)");
-    if (a->upsum.p && !conv_fuses_upsum(a)) return ssdn_set_error("conv: fused upsum requested for a launch that cannot fuse it (ssdn_conv_fuses_upsum)");
-    if (a->pool.p && !conv_fuses_pool(a)) return ssdn_set_error("conv: fused max-pool requested for a launch that cannot fuse it (ssdn_conv_fuses_pool)");
-    if (conv_use_gemm(a)) return launch_gemm_dma(a, s);
-    if (conv_use_thin(a)) return launch_conv_thin(a, nullptr, s);
-    if (conv_use_dma(a)) return launch_conv_dma(a, s);
-    if (conv_use_conv16(a)) return launch_conv16(a, s);
-    ConvGeom g = conv_geom(a->ltw, a->lth, a->ltn, a->ntaps, a->dy, a->dx, a->N, a->H, a->W, a->kc);
+    if ((a->sign_out || a->mask_sign || a->upsum_mask_sign) && !route_signs(a, r)) return ssdn_set_error("conv: sign bytes requested for a launch that cannot write / read them (ssdn_conv_signs)");
+    if (a->urot.p && r.kernel != CONV_K_CDMA) return ssdn_set_error("conv: fused UNROT_FWD requested for a launch that cannot fuse it (ssdn_conv_fuses_urot)");
+    if (a->unrot.p && r.kernel != CONV_K_GDMA) return ssdn_set_error("conv: fused UNROT_BWD requested for a launch that cannot fuse it (ssdn_conv_fuses_unrot)");
+    if (a->upsum.p && !route_fuses_upsum(a, r)) return ssdn_set_error("conv: fused upsum requested for a launch that cannot fuse it (ssdn_conv_fuses_upsum)");
+    if (a->pool.p && !route_fuses_pool(a, r)) return ssdn_set_error("conv: fused max-pool requested for a launch that cannot fuse it (ssdn_conv_fuses_pool)");
+    switch (r.kernel) {
+        case CONV_K_GDMA: return launch_gemm_dma(a, s);
+        case CONV_K_THIN: return launch_conv_thin(a, nullptr, s);
+        case CONV_K_CDMA: return launch_conv_dma(a, s);
+        case CONV_K_CONV16: return launch_conv16(a, s);
+        case CONV_K_CONV: break;            // below: geom and mt1 are the route's
+    }
+    const ConvGeom& g = r.geom;
     ConvAux x;
     x.mg_hw = magic_of(g.HW);
     x.mg_hh = magic_of(g.HH);
@@ -986,19 +991,13 @@ int launch_conv(const ssdn_conv_args* a, hipStream_t s) {
     // workgroups, each with a third of the MFMA and epilogue work.
     int full = a->Mpad / 96, rem = (a->Mpad % 96) / 32;
     const bool bf = a->bf16 != 0;
-    if (conv_uses_mt1(a, g)) {
-        rc = bf ? conv_launch_ks<1, true>(a, g, x, a->Mpad / 32, s) : conv_launch_ks<1, false>(a, g, x, a->Mpad / 32, s);
-        if (rc) return rc;
-        SSDN_CHECK_HIP(hipGetLastError());
-        return 0;
+    if (r.mt1) rc = bf ? conv_launch_ks<1, true>(a, g, x, a->Mpad / 32, s) : conv_launch_ks<1, false>(a, g, x, a->Mpad / 32, s);
+    else {
+        if (full) rc = bf ? conv_launch_ks<3, true>(a, g, x, full, s) : conv_launch_ks<3, false>(a, g, x, full, s);
+        x.m_base = full * 96;
+        if (!rc && rem == 2) rc = bf ? conv_launch_ks<2, true>(a, g, x, 1, s) : conv_launch_ks<2, false>(a, g, x, 1, s);
+        else if (!rc && rem == 1) rc = bf ? conv_launch_ks<1, true>(a, g, x, 1, s) : conv_launch_ks<1, false>(a, g, x, 1, s);
     }
-    if (full) {
-        rc = bf ? conv_launch_ks<3, true>(a, g, x, full, s) : conv_launch_ks<3, false>(a, g, x, full, s);
-        if (rc) return rc;
-    }
-    x.m_base = full * 96;
-    if (rem == 2) rc = bf ? conv_launch_ks<2, true>(a, g, x, 1, s) : conv_launch_ks<2, false>(a, g, x, 1, s);
-    else if (rem == 1) rc = bf ? conv_launch_ks<1, true>(a, g, x, 1, s) : conv_launch_ks<1, false>(a, g, x, 1, s);
     if (rc) return rc;
     SSDN_CHECK_HIP(hipGetLastError());
     return 0;

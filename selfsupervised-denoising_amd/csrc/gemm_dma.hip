@@ -449,8 +449,7 @@ static int gd_launch(const ssdn_conv_args* a, hipStream_t s, const ssdn_conv_arg
     if (a4) { x.w4 = (const h16*)a4->w; x.b4 = a4->bias; x.out32 = a4->dst32; x.M4 = a4->M; x.act4 = a4->act; }
     const int kreal = a->kreal > 0 ? a->kreal : a->Ktot;
     prof_begin(SSDN_PROF_GEMM, s);
-    int cus = ssdn_device_cus();
-    if (cus <= 0) cus = 256;
+    const int cus = ssdn_cus_or_default();
     const int grid = x.ntiles < cus ? x.ntiles : cus;           // persistent: one workgroup per CU (LDS-bound occupancy)
     SSDN_LAUNCH((k_gdma<WP, WM, NWP, NWM, BF, EPI>), dim3(grid), dim3(64 * NWP * NWM), LDS, s, *a, x);
     prof_end(SSDN_PROF_GEMM, s, 2.0 * px * a->M * kreal, px * (a->c0 + a->M) * 2.0);

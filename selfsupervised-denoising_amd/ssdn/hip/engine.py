@@ -165,39 +165,25 @@ class DeviceNet:
             return op.type, L.PackInputArgs(_ptr(self.t[a["src"]]), self._view(a["dst"]), a["B"], a["C"], a["H"], a["W"], a["R"], a["cpad"])
         if op.type == "conv":
             l = self._layer(a["layer"])
-            s = L.ConvArgs()
-            s.src0, s.src1 = self._view(a["src0"]), self._view(a["src1"])
-            s.c0, s.c1, s.up0 = a["c0"], a["c1"], a["up0"]
-            s.N, s.H, s.W = a["N"], a["H"], a["W"]
-            s.ntaps = len(a["taps"])
-            for i, (dy, dx) in enumerate(a["taps"]):
-                s.dy[i], s.dx[i] = dy, dx
-            s.w = _ptr(self.t[P + ("wf/" if a["role"] == "fwd" else "wd/") + a["layer"]])
-            wc = self.t.get(P + ("wfc/" if a["role"] == "fwd" else "wdc/") + a["layer"])
-            s.wc = _ptr(wc) if wc is not None else None
-            s.M, s.Mpad, s.Ktot = a["M"], a["Mpad"], a["Ktot"]
-            s.bias = self._pp(l.b_off) if a["bias"] else None
-            s.act = a["act"]
-            s.mask, s.add, s.dst = self._view(a["mask"]), self._view(a["add"]), self._view(a["dst"])
-            s.dst32 = _ptr(self.t[a["dst32"]]) if a["dst32"] is not None else None
-            s.ltw, s.lth, s.ltn, s.kc = a["ltw"], a["lth"], a["ltn"], a["kc"]
-            s.bf16 = a["bf16"]
-            s.kreal = a.get("kreal", 0)
-            s.pool, s.pool_shifted = self._view(a.get("pool")), a.get("pool_shifted", 0)
+            fwd = a["role"] == "fwd"
+
+            def ptr(field, name):
+                if field == "w":
+                    return _ptr(self.t[P + ("wf/" if fwd else "wd/") + name])
+                if field == "wc":      # the chunk-major copy, where the plan has one
+                    wc = self.t.get(P + ("wfc/" if fwd else "wdc/") + name)
+                    return _ptr(wc) if wc is not None else None
+                if field == "bias":
+                    return self._pp(l.b_off)
+                return _ptr(self.t[name])
+            s = L.conv_args(a, self._view, ptr)
+            # the planner's rules against the library's (the planner restates them: ssdn/hip/graph.py)
             if a.get("pool") is not None and not L.load().ssdn_conv_fuses_pool(C.byref(s)):
                 raise L.SsdnHipError("conv %s: the plan fuses the max-pool but the library cannot (planner / library rule mismatch)" % a["layer"])
-            s.upsum, s.upsum_mask, s.upsum_c = self._view(a.get("upsum")), self._view(a.get("upsum_mask")), a.get("upsum_c", 0)
             if a.get("upsum") is not None and not L.load().ssdn_conv_fuses_upsum(C.byref(s)):
                 raise L.SsdnHipError("conv %s: the plan fuses UPSUM_BWD but the library cannot (planner / library rule mismatch)" % a["layer"])
-            s.unrot, s.unrot_mask = self._view(a.get("unrot")), self._view(a.get("unrot_mask"))
-            s.unrot_smask = self.t[a["unrot_smask"]].data_ptr() if a.get("unrot_smask") else None
-            s.sign_out = self.t[a["sign_out"]].data_ptr() if a.get("sign_out") else None
-            s.mask_sign = self.t[a["mask_sign"]].data_ptr() if a.get("mask_sign") else None
-            s.upsum_mask_sign = self.t[a["upsum_mask_sign"]].data_ptr() if a.get("upsum_mask_sign") else None
             if (a.get("sign_out") or a.get("mask_sign") or a.get("upsum_mask_sign")) and not L.load().ssdn_conv_signs(C.byref(s)):
                 raise L.SsdnHipError("conv %s: the plan uses sign bytes but the library cannot (planner / library rule mismatch)" % a["layer"])
-            s.urot = self._view(a.get("urot"))
-            s.urot_smask = self.t[a["urot_smask"]].data_ptr() if a.get("urot_smask") else None
             if a.get("urot") is not None and not L.load().ssdn_conv_fuses_urot(C.byref(s)):
                 raise L.SsdnHipError("conv %s: the plan fuses UNROT_FWD but the library cannot (planner / library rule mismatch)" % a["layer"])
             if a.get("unrot") is not None and not L.load().ssdn_conv_fuses_unrot(C.byref(s)):

@@ -198,6 +198,33 @@ SYMBOLS = ["ssdn_run_ops", "ssdn_stream_order", "ssdn_conv_lds_bytes", "ssdn_wgr
 PLAN_PHASES = dict(repack=0, forward=1, backward=2, optimiser=3)
 PROF = dict(conv_mt3=0, conv_mt2=1, conv_mt1=2, wgrad=3, gemm=4, cdma_mt3=5, cdma_mt21=6, wgrad_side=7)
 
+CONV_SIGN_FIELDS = ("unrot_smask", "urot_smask", "sign_out", "mask_sign", "upsum_mask_sign")
+
+
+def conv_args(a: dict, view, ptr) -> ConvArgs:
+    """ssdn_conv_args of a planned SSDN_OP_CONV (the dict ssdn.hip.graph.NetPlan._conv writes): the one place that knows which key fills
+    which field.  Where the addresses come from is the caller's: view(v) -> View for a planned view or None; ptr(field, name) -> address
+    or None, asked for `w` and `wc` (name: the layer), for `bias` (the layer) where the op has one, and for `dst32` and the five sign-byte
+    fields (the plan's tensor name) where the plan names one."""
+    s = ConvArgs()
+    s.src0, s.src1 = view(a["src0"]), view(a["src1"])
+    s.c0, s.c1, s.up0, s.N, s.H, s.W, s.ntaps = a["c0"], a["c1"], a["up0"], a["N"], a["H"], a["W"], len(a["taps"])
+    for t, (dy, dx) in enumerate(a["taps"]):
+        s.dy[t], s.dx[t] = dy, dx
+    s.w, s.wc = ptr("w", a["layer"]), ptr("wc", a["layer"])
+    s.M, s.Mpad, s.Ktot, s.act = a["M"], a["Mpad"], a["Ktot"], a["act"]
+    s.bias = ptr("bias", a["layer"]) if a["bias"] else None
+    s.mask, s.add, s.dst = view(a["mask"]), view(a["add"]), view(a["dst"])
+    s.dst32 = ptr("dst32", a["dst32"]) if a["dst32"] is not None else None
+    s.ltw, s.lth, s.ltn, s.kc, s.bf16, s.kreal = a["ltw"], a["lth"], a["ltn"], a["kc"], a["bf16"], a.get("kreal", 0)
+    s.pool, s.pool_shifted = view(a.get("pool")), a.get("pool_shifted", 0)
+    s.upsum, s.upsum_mask, s.upsum_c = view(a.get("upsum")), view(a.get("upsum_mask")), a.get("upsum_c", 0)
+    s.unrot, s.unrot_mask, s.urot = view(a.get("unrot")), view(a.get("unrot_mask")), view(a.get("urot"))
+    for k in CONV_SIGN_FIELDS:
+        setattr(s, k, ptr(k, a[k]) if a.get(k) is not None else None)
+    return s
+
+
 def pointer_fields(st, base: int = 0):
     """byte offsets of every pointer inside a (nested) argument struct: c_void_p fields and the `p` of ssdn_view"""
     out = []

@@ -7,8 +7,8 @@ fp32 in any order, so that the expected output is an integer that does not depen
 equality (check_ints).  device=False builds the operands and the argument struct without a GPU (the pointers are placeholders): the
 host-side queries of the library and the reference need no more.
 
-Used by tests/test_hip_conv16.py (k_conv16 against k_conv) and tests/test_hip_cdma_walk.py / tests/test_cdma_walk_cpu.py (k_cdma's tile
-walk)."""
+Used by tests/test_hip_conv16.py (k_conv16 against k_conv), tests/test_hip_cdma_walk.py / tests/test_cdma_walk_cpu.py (k_cdma's tile
+walk) and tests/test_hip_conv_route.py (one launch per kernel of SSDN_OP_CONV; the 1x1 layers are its only tap sets of another length)."""
 import ctypes as C
 
 import torch
@@ -61,7 +61,7 @@ class Case:
 
     def __init__(self, role, N, c0, c1, up0, M, taps, H=16, W=16, mask=False, add=False, upsum_c=0, bias=None, seed=0, dst32=False,
                  edge=False, cm=False, ints=False, sign_out=False, mask_sign=False, upsum_mask_sign=False, urot=False, urot_smask=False,
-                 device=True):
+                 kreal=0, device=True):
         from ssdn.hip.graph import choose_conv_tile
         L, lib = _lib()
         self.role, self.N, self.H, self.W, self.c0, self.c1, self.up0, self.M, self.upsum_c = role, N, H, W, c0, c1, up0, M, upsum_c
@@ -105,6 +105,8 @@ class Case:
         else:
             s0 = _rand(gen, (N, hs, ws, c0)) if c0 else None
             s1 = _rand(gen, (N, H, W, c1)) if c1 else None
+        if kreal:                 # a first layer: kreal real input channels, the slots behind them hold zeros (ssdn_conv_args.kreal)
+            s0[..., kreal:] = 0
         if edge:
             # non-zero only where the halo's zero fill begins: the two rows next to the rows above (forward) / below (data gradient) the
             # image, and the left and right columns
@@ -122,7 +124,7 @@ class Case:
         if ints:
             self.w, self.bias, self.mask, self.add, self.umask = w.to(self.dt), bias_t, mask_t, add_t, umask_t
         else:
-            w = _rand(gen, (9, self.Mpad, self.Ktot), 1.0 / (3.0 * self.Ktot ** 0.5))
+            w = _rand(gen, (len(self.taps), self.Mpad, self.Ktot), 1.0 / (3.0 * self.Ktot ** 0.5))
             w[:, M:] = 0
             self.w = w.to(self.dt)
             self.bias = _rand(gen, (M,), 0.3) if (bias if bias is not None else not bf) else None
@@ -137,7 +139,7 @@ class Case:
             _, a.src0 = view(self.s0)
         if c1:
             _, a.src1 = view(self.s1)
-        a.c0, a.c1, a.up0, a.N, a.H, a.W, a.ntaps = c0, c1, int(up0), N, H, W, 9
+        a.c0, a.c1, a.up0, a.N, a.H, a.W, a.ntaps = c0, c1, int(up0), N, H, W, len(self.taps)
         for t, (dy, dx) in enumerate(self.taps):
             a.dy[t], a.dx[t] = dy, dx
         a.w, a.M, a.Mpad, a.Ktot = (self.dw.data_ptr() if device else 0x1000), M, self.Mpad, self.Ktot
@@ -152,7 +154,9 @@ class Case:
             _, a.add = view(self.add)
         self.outs = {}
         self.bytes_out = {}       # sign-byte outputs: poisoned with 0xA5
-        if dst32:
+        if dst32 and not device:
+            a.dst32 = 0x1000
+        elif dst32:
             self.outs["dst32"] = torch.empty(N, M, H, W, device=_dev())
             a.dst32 = self.outs["dst32"].data_ptr()
         elif urot:
@@ -171,7 +175,7 @@ class Case:
             a.upsum_c = upsum_c
         cus = lib.ssdn_device_cus()
         a.ltw, a.lth, a.ltn, a.kc = choose_conv_tile(N, H, W, self.taps, self.Ktot, self.Mpad, out16=not dst32, cus=cus if cus > 0 else 256)
-        a.bf16, a.kreal = int(bf), self.Ktot
+        a.bf16, a.kreal = int(bf), kreal or self.Ktot
         if cm:
             # the chunk-major copy SSDN_OP_WPACK writes next to the shadow (ssdn_conv_args.wc), by the host model tests/test_hip_optimiser.py
             # holds that op to: chunks of 48 input channels, then one optional chunk of 16

@@ -139,31 +139,12 @@ def test_chunk_major_copy_of_the_builder():
 
 PLANS = [(3, 9, True, 32, 64, 64, True), (3, 9, True, 1, 512, 512, False), (3, 9, True, 1, 768, 768, False), (3, 3, False, 1, 352, 512, False),
          (3, 3, False, 1, 512, 352, False)]
-DUMMY = 0x1000          # a non-null address: the queries read no memory
 
 
 def _plan_args(plan, a):
-    from ssdn.hip import lib as L
-    s = L.ConvArgs()
-
-    def view(v):
-        return L.View(DUMMY, plan.tensors[v.t].shape[-1], v.co) if v is not None else L.View(None, 0, 0)
-    s.src0, s.src1 = view(a["src0"]), view(a["src1"])
-    s.c0, s.c1, s.up0, s.N, s.H, s.W, s.ntaps = a["c0"], a["c1"], a["up0"], a["N"], a["H"], a["W"], len(a["taps"])
-    for t, (dy, dx) in enumerate(a["taps"]):
-        s.dy[t], s.dx[t] = dy, dx
-    s.w, s.M, s.Mpad, s.Ktot, s.act = DUMMY, a["M"], a["Mpad"], a["Ktot"], a["act"]
-    s.wc = DUMMY if plan.prefix + ("wfc/" if a["role"] == "fwd" else "wdc/") + a["layer"] in plan.tensors else None
-    s.bias = DUMMY if a["bias"] else None
-    s.mask, s.add, s.dst = view(a["mask"]), view(a["add"]), view(a["dst"])
-    s.dst32 = DUMMY if a["dst32"] is not None else None
-    s.ltw, s.lth, s.ltn, s.kc, s.bf16, s.kreal = a["ltw"], a["lth"], a["ltn"], a["kc"], a["bf16"], a.get("kreal", 0)
-    s.pool, s.pool_shifted = view(a.get("pool")), a.get("pool_shifted", 0)
-    s.upsum, s.upsum_mask, s.upsum_c = view(a.get("upsum")), view(a.get("upsum_mask")), a.get("upsum_c", 0)
-    s.unrot, s.unrot_mask, s.urot = view(a.get("unrot")), view(a.get("unrot_mask")), view(a.get("urot"))
-    for k in ("unrot_smask", "urot_smask", "sign_out", "mask_sign", "upsum_mask_sign"):
-        setattr(s, k, DUMMY if a.get(k) is not None else None)
-    return s
+    """dummy addresses, the plan's own strides, and the chunk-major weight copy where the plan has one"""
+    from gen_golden_routes import plan_args
+    return plan_args(plan, a)
 
 
 @pytest.mark.parametrize("cin,cout,bs,Bn,H,W,train", PLANS)

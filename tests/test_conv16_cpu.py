@@ -17,25 +17,10 @@ PLANS = [(3, 9, True, 32, 64, 64), (3, 9, True, 2, 64, 64), (3, 1, False, 32, 64
 
 
 def _args(a):
-    s = L.ConvArgs()
-
+    """dummy addresses, every view 160 channels wide, no chunk-major weight copy"""
     def view(v):
         return L.View(DUMMY, 160, v.co) if v is not None else L.View(None, 0, 0)
-    s.src0, s.src1 = view(a["src0"]), view(a["src1"])
-    s.c0, s.c1, s.up0, s.N, s.H, s.W, s.ntaps = a["c0"], a["c1"], a["up0"], a["N"], a["H"], a["W"], len(a["taps"])
-    for t, (dy, dx) in enumerate(a["taps"]):
-        s.dy[t], s.dx[t] = dy, dx
-    s.w, s.M, s.Mpad, s.Ktot, s.act = DUMMY, a["M"], a["Mpad"], a["Ktot"], a["act"]
-    s.bias = DUMMY if a["bias"] else None
-    s.mask, s.add, s.dst = view(a["mask"]), view(a["add"]), view(a["dst"])
-    s.dst32 = DUMMY if a["dst32"] is not None else None
-    s.ltw, s.lth, s.ltn, s.kc, s.bf16, s.kreal = a["ltw"], a["lth"], a["ltn"], a["kc"], a["bf16"], a["kreal"]
-    s.pool, s.pool_shifted = view(a["pool"]), a["pool_shifted"]
-    s.upsum, s.upsum_mask, s.upsum_c = view(a["upsum"]), view(a["upsum_mask"]), a["upsum_c"]
-    s.unrot, s.unrot_mask, s.urot = view(a["unrot"]), view(a["unrot_mask"]), view(a["urot"])
-    for k in ("unrot_smask", "urot_smask", "sign_out", "mask_sign", "upsum_mask_sign"):
-        setattr(s, k, DUMMY if a[k] is not None else None)
-    return s
+    return L.conv_args(a, view, lambda field, name: None if field == "wc" else DUMMY)
 
 
 def _rule(a, roles, cus):
