@@ -74,7 +74,9 @@ enum ssdn_op_type {
     SSDN_OP_ACCUM = 25,        /* dst[i] = fl(dst[i] + src[i]): folds a per-pass staging value into a running gradient sum */
     SSDN_OP_HEAD_POSTERIOR = 26, /* per-pixel posterior of the SSDN head beyond its mean: covariance, std maps, samples (no planned list holds it) */
     SSDN_OP_SSIM = 27,          /* per-sample SSIM of two image batches over each sample's un-padded extent, optional SSIM map (no planned list holds it) */
-    SSDN_OP_CALIBRATION = 28    /* per-sample calibration statistics of the posterior N(mean, cov) against the clean image, optional z histogram / z map (no planned list holds it) */
+    SSDN_OP_CALIBRATION = 28,   /* per-sample calibration statistics of the posterior N(mean, cov) against the clean image, optional z histogram / z map (no planned list holds it) */
+    SSDN_OP_IMAGE_IN = 29,      /* whole uint8 images of differing sizes -> the padded fp32 input batch: / 255, transposed, reflection-padded (no planned list holds it) */
+    SSDN_OP_IMAGE_OUT = 30      /* an fp32 batch -> uint8 images of differing sizes: cropped to each extent, clipped, * 255, truncated, transposed (no planned list holds it) */
 };
 
 /* One record of the op list.  `args` points at the matching ssdn_*_args struct (host memory).
@@ -672,6 +674,46 @@ typedef struct ssdn_calibration_args {
     void* scratch;                /* per-workgroup partial sums and counts (8 bytes each) */
     int64_t scratch_bytes;
 } ssdn_calibration_args;
+
+/* ---- SSDN_OP_IMAGE_IN / SSDN_OP_IMAGE_OUT ---------------------------------------------------------
+ * Whole images of differing sizes into and out of the engine as bytes: what NoisyDataset.pad_to_output_size / unpad and
+ * ssdn.utils.tensor2image do on the host for one image at a time, as one launch per batch and direction.
+ * Images are what PIL hands out: upright uint8, row-major, channels interleaved, img[y][x][c] of h x w x C with the tight pitch w C,
+ * C = 1 or 3.  The B images of a batch lie in one byte buffer, image b from byte offs[b] on; gaps between them are allowed.
+ * Tensors keep the package's swapped axes (datasets/folder.py, hdf5.py): tensor axis 2 runs along the image's x, axis 3 along its y, and
+ * ext[b] = (e1, e2) = (w_b, h_b) is the un-padded extent on axes 2 and 3 (SSDN_OP_METRICS' convention).  Both ops fold the transposition.
+ * IMAGE_IN, every element of dst [B,C,H,W]:
+ *     dst[b,c,i,j] = (float)src_b[(r(j, e2) e1 + r(i, e1)) C + c] / 255.f        (a true division, as SSDN_OP_NOISE's and to_tensor's)
+ *     r(k, 1) = 0;  otherwise p = 2 (n - 1), m = k mod p, r(k, n) = m < n ? m : p - m   (numpy's "reflect" for any pad length)
+ *   bit for bit to_tensor, .permute(0, 2, 1), NoisyDataset.pad_to_output_size of every image.
+ * IMAGE_OUT, for x < e1, y < e2:
+ *     dst_b[(y e1 + x) C + c] = q(x[b,c,x,y]),   q(v) = (uint8) trunc(fl(min(max(v, 0), 1) * 255.f)),   q(NaN) = 0
+ *   which is tensor2image's np.uint8(np.clip(a, 0, 1) * 255) of the un-padded image; no byte outside an image's h_b w_b C bytes is written.
+ * ext and offs are device memory the host has not seen: both kernels clamp ext to [0,H] x [0,W] and touch byte offs[b] + index only if it
+ * lies inside [0, src_bytes) (dst_bytes); a read outside yields 0, a write outside is dropped, a sample with an empty extent becomes
+ * zeros (in) or writes nothing (out).  Inconsistent tables never become an access outside the buffers.
+ * Kernels (csrc/image_io.hip): one workgroup per (32 x 64 tile of tensor axes 2 x 3, sample) -- of the padded
+ * tensor (in) or of the extent (out) --, the transposition through an LDS tile of odd pitch; bytes are touched along x, planes along axis 3.
+ * Argument errors are raised before any device call (text prefixed "image_in:" / "image_out:"): a NULL pointer, C not 1 or 3, B, H or
+ * W < 1, a negative byte count, B or the tile rows ceil(H / 32) above 65535.  Adding these ops changed no existing struct: the ABI version
+ * stays. */
+typedef struct ssdn_image_in_args {
+    const uint8_t* src;   /* packed images, device */
+    int64_t src_bytes;
+    const int64_t* offs;  /* device [B] */
+    const int32_t* ext;   /* device [B][2] = (w_b, h_b) */
+    int32_t B, C, H, W;
+    float* dst;           /* out [B,C,H,W]: every element is written */
+} ssdn_image_in_args;
+
+typedef struct ssdn_image_out_args {
+    const float* x;       /* [B,C,H,W] */
+    const int32_t* ext;   /* device [B][2] = (w_b, h_b) */
+    const int64_t* offs;  /* device [B] */
+    uint8_t* dst;         /* packed images out, device */
+    int64_t dst_bytes;
+    int32_t B, C, H, W;
+} ssdn_image_out_args;
 
 /* ---- SSDN_OP_INPUT_GRAD --------------------------------------------------------------------
  * replaces: the data gradient autograd propagates into the network input through the first conv (noise_network.py:69-71) and the

@@ -112,6 +112,8 @@ int ssdn_struct_size(int op_type) {
         case SSDN_OP_HEAD_POSTERIOR: return (int)sizeof(ssdn_head_posterior_args);
         case SSDN_OP_SSIM: return (int)sizeof(ssdn_ssim_args);
         case SSDN_OP_CALIBRATION: return (int)sizeof(ssdn_calibration_args);
+        case SSDN_OP_IMAGE_IN: return (int)sizeof(ssdn_image_in_args);
+        case SSDN_OP_IMAGE_OUT: return (int)sizeof(ssdn_image_out_args);
         default: return -1;
     }
 }
@@ -411,6 +413,8 @@ int ssdn_run_ops(const ssdn_op* ops, int n, void* stream) {
             case SSDN_OP_HEAD_POSTERIOR: rc = launch_head_posterior((const ssdn_head_posterior_args*)p, s); break;
             case SSDN_OP_SSIM: rc = launch_ssim((const ssdn_ssim_args*)p, s); break;
             case SSDN_OP_CALIBRATION: rc = launch_calibration((const ssdn_calibration_args*)p, s); break;
+            case SSDN_OP_IMAGE_IN: rc = launch_image_in((const ssdn_image_in_args*)p, s); break;
+            case SSDN_OP_IMAGE_OUT: rc = launch_image_out((const ssdn_image_out_args*)p, s); break;
             case SSDN_OP_ZERO: {
                 const ssdn_zero_args* z = (const ssdn_zero_args*)p;
                 if (z->bytes & 15) return ssdn_set_error("op %d: zero size must be a multiple of 16", i);

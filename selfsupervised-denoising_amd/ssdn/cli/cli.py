@@ -1,4 +1,5 @@
-"""`ssdn` command line (cli/cli.py:8-44 of the reference): `ssdn train start ...`, `ssdn train resume RUN_DIR`, `ssdn eval ...`."""
+"""`ssdn` command line (cli/cli.py:8-44 of the reference): `ssdn train start ...`, `ssdn train resume RUN_DIR`, `ssdn eval ...`; and
+`ssdn denoise ...`, which the reference does not have."""
 import argparse
 from typing import List, Optional
 
@@ -6,6 +7,7 @@ from ssdn.version import __version__
 
 
 def build_parser():
+    from ssdn.cli.cmds.denoise import DenoiseCommand
     from ssdn.cli.cmds.eval import EvaluateCommand
     from ssdn.cli.cmds.train import TrainCommand
     parser = argparse.ArgumentParser(prog="ssdn", description="Training and evaluation of blind-spot denoisers (SSDN, Noise2Clean, "
@@ -13,7 +15,7 @@ def build_parser():
     parser.add_argument("--version", action="version", version="%(prog)s v" + __version__)
     subs = parser.add_subparsers(dest="command", required=True)
     cmds = {}
-    for c in (TrainCommand(), EvaluateCommand()):
+    for c in (TrainCommand(), EvaluateCommand(), DenoiseCommand()):
         c.configure(subs)
         cmds[c.cmd()] = c
     return parser, cmds

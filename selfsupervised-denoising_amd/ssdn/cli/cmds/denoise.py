@@ -1,0 +1,79 @@
+"""`ssdn denoise --model M --input I --output O [--noise_param P] [--batch_size B] [--bucket N] [--uniform] [--std] [--recursive]`:
+denoise already noisy images with a trained model (the reference has no such command: its evaluator takes clean datasets and adds
+the noise itself).  I: an image file or a folder of images (file discovery and channel conversion of datasets/folder.py); writes
+O/<relative stem>.png, with --std O/<relative stem>_std.npy (float32 [C,h,w] posterior std dev, ssdn models only), and O/denoise.csv
+with one row per image.  PNG decode and encode stay on the host with PIL; everything between is `Denoiser.denoise`."""
+import os
+from typing import Dict, List, Tuple
+
+from ssdn.cli.cmds.cmd import Command
+
+
+def find_images(path: str, recursive: bool = False) -> Tuple[str, List[str]]:
+    """-> (the directory relative stems are taken from, the image files under `path` in the order of UnlabelledImageFolderDataset)"""
+    from ssdn.datasets.folder import UnlabelledImageFolderDataset, is_image_file
+    path = os.path.expanduser(path)
+    if os.path.isfile(path):
+        if not is_image_file(path):
+            raise ValueError("denoise: %s is not an image file" % path)
+        return os.path.dirname(path), [path]
+    if not os.path.isdir(path):
+        raise FileNotFoundError("denoise: no such file or folder: %s" % path)
+    return path, UnlabelledImageFolderDataset(path, recursive=recursive).files
+
+
+class DenoiseCommand(Command):
+    def cmd(self) -> str:
+        return "denoise"
+
+    def configure(self, parser):
+        p = parser.add_parser(self.cmd(), help="Denoise noisy images with a pre-trained model.")
+        p.add_argument("--model", "-m", required=True, help="Path to model weights (.wt) or training file (.training).")
+        p.add_argument("--input", "-i", required=True, help="A noisy image file or a folder of noisy images.")
+        p.add_argument("--output", "-o", required=True, help="Directory the denoised PNGs and denoise.csv are written to.")
+        p.add_argument("--noise_param", default=None,
+                       help="The noise parameter of the images, for ssdn models trained with a known one: the numeric part of the "
+                            "noise style (gauss: an integer is /255; poisson: lambda; impulse: an integer is per cent).")
+        p.add_argument("--batch_size", type=int, default=1, help="Images of one padded shape per batch.")
+        p.add_argument("--bucket", type=int, default=None,
+                       help="Pad every image to a multiple of this (a multiple of 32; default 32): fewer distinct plans for more padding.")
+        p.add_argument("--uniform", action="store_true", help="Pad every image to the largest one (one plan for the whole folder).")
+        p.add_argument("--std", action="store_true",
+                       help="Also write <stem>_std.npy: the per-pixel posterior std dev, float32 [C,h,w] (ssdn models only).")
+        p.add_argument("--recursive", action="store_true", help="Also take the images of the folder's sub-folders.")
+
+    def execute(self, args: Dict):
+        import numpy as np
+        import torch
+        from PIL import Image
+        from ssdn.denoiser import Denoiser
+        from ssdn.params import ConfigValue
+        from ssdn.utils.data import set_color_channels
+        sd = torch.load(args["model"], map_location="cpu", weights_only=False)
+        denoiser = Denoiser.from_state_dict(sd["denoiser"] if "denoiser" in sd else sd)
+        channels = denoiser.cfg[ConfigValue.IMAGE_CHANNELS]
+        opts = dict(noise_param=args.get("noise_param"), batch_size=args.get("batch_size") or 1, bucket=args.get("bucket"),
+                    uniform=bool(args.get("uniform")), std=bool(args.get("std")))
+        denoiser.denoise([], **opts)                    # (the model's refusals, before a file is opened or a directory made)
+        base, files = find_images(args["input"], bool(args.get("recursive")))
+        images = []
+        for path in files:
+            with open(path, "rb") as f:
+                img = Image.open(f)
+                img.load()
+            images.append(np.asarray(set_color_channels(img, channels), dtype=np.uint8))
+        res = denoiser.denoise(images, **opts)
+        out_dir = args["output"]
+        os.makedirs(out_dir, exist_ok=True)
+        with open(os.path.join(out_dir, "denoise.csv"), "w") as csv:
+            csv.write(",".join(["file", "width", "height"] + (["noise_std"] if "noise_std" in res else [])) + "\n")
+            for k, path in enumerate(files):
+                stem = os.path.splitext(os.path.relpath(path, base))[0]
+                os.makedirs(os.path.dirname(os.path.join(out_dir, stem)) or out_dir, exist_ok=True)
+                Image.fromarray(res["out"][k].numpy()).save(os.path.join(out_dir, stem + ".png"))
+                if "std" in res:
+                    np.save(os.path.join(out_dir, stem + "_std.npy"), res["std"][k].numpy().astype(np.float32))
+                h, w = images[k].shape[:2]
+                csv.write(",".join([os.path.relpath(path, base), str(w), str(h)]
+                                   + (["{:.6f}".format(res["noise_std"][k])] if "noise_std" in res else [])) + "\n")
+        return res

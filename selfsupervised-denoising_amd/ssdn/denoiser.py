@@ -390,6 +390,121 @@ class Denoiser(nn.Module):
         res["mean"] = out[PipelineOutput.IMG_DENOISED]
         return res
 
+    def _noise_param_value(self, noise_param) -> Optional[float]:
+        """`denoise`'s noise_param as the value Metadata.INPUT_NOISE_VALUES carries: the numeric part of the model's noise style in
+        the style grammar (ssdn.utils.noise.parse_style) -- gauss: an integer is /255; poisson: lambda; impulse: an integer is per
+        cent.  Required for a known-noise SSDN model and refused for every other one (ValueError)."""
+        from ssdn.utils import noise
+        known = self._pipeline == Pipeline.SSDN and self.cfg[ConfigValue.NOISE_VALUE] == NoiseValue.KNOWN
+        if not known:
+            if noise_param is not None:
+                raise ValueError("denoise: noise_param is for ssdn models trained with a known noise parameter; this model takes none")
+            return None
+        if noise_param is None:
+            raise ValueError("denoise: this model was trained with a known noise parameter: noise_param is required")
+        kind = noise.parse_style(self.cfg[ConfigValue.NOISE_STYLE])[0]
+        try:
+            params = noise.parse_style(kind + str(noise_param).strip())[1]
+        except (ValueError, IndexError):
+            params = []
+        if len(params) != 1:
+            raise ValueError("denoise: noise_param %r is not one number in the grammar of a %s style" % (noise_param, kind))
+        v = params[0]
+        if v < 0:
+            raise ValueError("denoise: noise_param must not be negative, got %r" % (noise_param,))
+        if kind == "gauss":
+            return v / 255 if isinstance(v, int) else float(v)
+        if kind == "impulse":
+            return noise.impulse_alpha(v)
+        return float(v)
+
+    def denoise(self, images: List, noise_param=None, batch_size: int = 1, bucket: Optional[int] = None, uniform: bool = False,
+                std: bool = False) -> Dict:
+        """Denoise already noisy images.  images: uint8 arrays or tensors [h, w] or [h, w, C], upright as PIL hands them out, of any and
+        differing sizes, C the model's channel count.  Every image is reflection-padded bottom and right to a multiple of `bucket`
+        (default and unit: NoiseNetwork.input_wh_mul(); larger values trade padding for fewer distinct plans -- at most _MAX_ENGINES are
+        cached and one owns ~1 GB), to a square for a blind-spot model, with uniform=True to the largest image of the call (the
+        evaluator's pad_uniform); images of one padded shape run in batches of at most `batch_size`, a short last batch at its own size.
+        Per batch: one pinned upload of the packed bytes, SSDN_OP_IMAGE_IN (/ 255, transpose, pad), an inference run under no_grad
+        whatever the module's mode, SSDN_OP_IMAGE_OUT (crop, clip, * 255, truncate, transpose), one download (csrc/image_io.hip, DESIGN.md
+        section 3.16): the bytes `tensor2image` would give for the un-padded IMG_DENOISED of the same run.
+        noise_param: required for an ssdn model with a known noise parameter, refused (ValueError, before any device work) for every
+        other model; the numeric part of the noise style -- gauss: an integer is /255, poisson: lambda, impulse: an integer is per cent.
+        -> {"out": uint8 CPU tensors of the inputs' shapes, in input order}; ssdn models also "noise_std": per image the mean of
+        NOISE_STD_DEV over its extent; std=True (ssdn only) adds "std": float32 [C, h, w] upright posterior std maps (Denoiser.posterior's).
+        Like `posterior` it never becomes the forward that backward() / optimizer_step() / accumulate_metrics() act on."""
+        import numpy as np
+        Cn = self.cfg[ConfigValue.IMAGE_CHANNELS]
+        ssdn_pipe = self._pipeline == Pipeline.SSDN
+        value = self._noise_param_value(noise_param)
+        if std and not ssdn_pipe:
+            raise ValueError("denoise: std=True needs a posterior: the %s pipeline has none (ssdn models only)" % self._pipeline.value)
+        mul = NoiseNetwork.input_wh_mul()
+        bucket = mul if bucket is None else int(bucket)
+        if bucket < mul or bucket % mul:
+            raise ValueError("denoise: bucket must be a positive multiple of %d, got %d" % (mul, bucket))
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError("denoise: batch_size must be at least 1")
+        imgs = []
+        for k, im in enumerate(images):
+            t = im
+            if isinstance(im, np.ndarray):
+                a = np.ascontiguousarray(im)
+                t = torch.from_numpy(a if a.flags.writeable else a.copy())      # (PIL hands out read-only arrays)
+            if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() not in (2, 3):
+                raise ValueError("denoise: image %d is not a uint8 array or tensor [h, w] or [h, w, C]" % k)
+            t = t.detach().cpu()
+            t = (t.unsqueeze(-1) if t.dim() == 2 else t).contiguous()
+            if t.shape[2] != Cn:
+                raise ValueError("denoise: image %d has %d channel(s), the model takes %d" % (k, t.shape[2], Cn))
+            if t.shape[0] < 1 or t.shape[1] < 1:
+                raise ValueError("denoise: image %d is empty" % k)
+            imgs.append(t)
+        res: Dict = {"out": [None] * len(imgs)}
+        if ssdn_pipe:
+            res["noise_std"] = [None] * len(imgs)
+        if std:
+            res["std"] = [None] * len(imgs)
+        if not imgs:
+            return res
+        # padded shapes on tensor axes 2 and 3 = along the image's x and y (NoisyDataset.get_output_size: uniform, multiple, square)
+        big = (max(t.shape[1] for t in imgs), max(t.shape[0] for t in imgs))
+        groups: Dict[Tuple[int, int], List[int]] = {}
+        for k, t in enumerate(imgs):
+            H, W = ((n + bucket - 1) // bucket * bucket for n in (big if uniform else (t.shape[1], t.shape[0])))
+            if self.cfg[ConfigValue.BLINDSPOT]:
+                H = W = max(H, W)
+            groups.setdefault((H, W), []).append(k)
+        keep = (self._last_engine, getattr(self, "_has_loss_last", None))
+        try:
+            with torch.no_grad():
+                for (H, W), members in groups.items():
+                    for lo in range(0, len(members), batch_size):
+                        idx = members[lo:lo + batch_size]
+                        B = len(idx)
+                        eng = self._engine(B, H, W, False)
+                        data = [eng.image_in([imgs[k] for k in idx])]
+                        if value is not None:
+                            data += [torch.zeros(0), {NoisyDataset.Metadata.INPUT_NOISE_VALUES: torch.full((B, 1, 1, 1), value)}]
+                        self._run(data, clone=False)         # (no_grad: the inference plan of this shape, whose input is already in place)
+                        outs = eng.image_out()
+                        smap = eng.posterior(cov=False, std=True)["std"].cpu() if std else None
+                        nstd = (eng.noise_std if eng.style == "poisson" else eng.noise_std.cpu()) if ssdn_pipe else None
+                        for b, k in enumerate(idx):
+                            h, w = imgs[k].shape[:2]
+                            o = outs[b].clone()
+                            res["out"][k] = o if images[k].ndim == 3 else o[:, :, 0]
+                            if ssdn_pipe:
+                                # gauss / impulse: one value per sample (a learnable scalar: one for all); poisson: a map
+                                res["noise_std"][k] = (float(nstd[b, :w, :h].mean()) if eng.style == "poisson"
+                                                       else float(nstd[0 if self._const else b]))
+                            if std:
+                                res["std"][k] = smap[b, :, :w, :h].permute(0, 2, 1).contiguous()
+        finally:
+            self._last_engine, self._has_loss_last = keep
+        return res
+
     def backward(self):
         """Run the planned backward pass of the last training-mode run_pipeline; gradients land in `flat_grad` and are
         visible as `.grad` of every parameter."""

@@ -357,6 +357,7 @@ class DenoiserEngine:
         self._post = {}             # posterior(): cov / std / samples buffers, allocated on first use (no plan tensor)
         self._ssim = {}             # ssim(): value / map / scratch buffers, allocated on first use (no plan tensor)
         self._calib = {}            # calibration(): stats / hist / zmap / scratch buffers, allocated on first use (no plan tensor)
+        self._img = {}              # image_in() / image_out(): pinned and device byte buffers with their tables, allocated on first use (no plan tensor)
 
     # ---- op construction -----------------------------------------------------------------------------------
     def _gmax(self, net: Optional[DeviceNet]):
@@ -690,6 +691,74 @@ class DenoiserEngine:
                               _ptr(buf["scratch"]), buf["scratch"].numel() * 8)
         OpList([("calibration", a)]).run(s)
         return buf["stats"], (buf["hist"] if want_hist else None), (buf["zmap"] if want_map else None)
+
+    IMAGE_ALIGN = 16            # image_in(): every image of a batch starts on a multiple of this in the packed byte buffer
+
+    def _image_buffers(self):
+        """The byte buffers of image_in() / image_out(), sized for a full batch of un-padded images of the engine's shape: [offs: B int64 |
+        ext: B x 2 int32 | the packed images], once pinned on the host and once on the device (one upload carries the tables and the
+        bytes), and the same pair for the images coming out."""
+        buf = self._img
+        if "dev_in" not in buf:
+            a = self.IMAGE_ALIGN
+            buf["head"] = (16 * self.B + a - 1) // a * a
+            n = buf["head"] + self.B * ((self.C * self.H * self.W + a - 1) // a * a)
+            buf["host_in"] = torch.zeros((n,), dtype=torch.uint8).pin_memory()
+            buf["host_out"] = torch.zeros((n,), dtype=torch.uint8).pin_memory()
+            buf["dev_in"] = torch.zeros((n,), dtype=torch.uint8, device=self.device)
+            buf["dev_out"] = torch.zeros((n,), dtype=torch.uint8, device=self.device)
+        return buf
+
+    def image_in(self, images: List[torch.Tensor]) -> torch.Tensor:
+        """Fill `self.inp` with a batch of whole images (SSDN_OP_IMAGE_IN, csrc/image_io.hip): one pinned upload of the packed bytes and
+        their tables, one launch that divides by 255, transposes to the package's swapped axes and reflection-pads every image bottom
+        and right to the engine's shape.  images: exactly B contiguous uint8 CPU tensors [h, w, C] (upright, as PIL hands them out) with
+        w <= H and h <= W of the engine (tensor axis 2 runs along x).  -> self.inp, which `Denoiser._run` then takes without a copy.
+        The tables stay on the device for the image_out() that follows."""
+        B, Cn = self.B, self.C
+        if len(images) != B:
+            raise L.SsdnHipError("image_in: %d images for an engine of batch %d" % (len(images), B))
+        for t in images:
+            if (t.dtype != torch.uint8 or t.device.type != "cpu" or t.dim() != 3 or t.shape[2] != Cn or not t.is_contiguous()
+                    or not (1 <= t.shape[1] <= self.H and 1 <= t.shape[0] <= self.W)):
+                raise L.SsdnHipError("image_in: every image must be a contiguous uint8 CPU tensor [h, w, %d] with w <= %d and h <= %d"
+                                     % (Cn, self.H, self.W))
+        buf = self._image_buffers()
+        host, a = buf["host_in"], self.IMAGE_ALIGN
+        offs, pos = [], 0
+        for t in images:
+            offs.append(pos)
+            host[buf["head"] + pos: buf["head"] + pos + t.numel()] = t.reshape(-1)
+            pos += (t.numel() + a - 1) // a * a
+        host[:8 * B].view(torch.int64).copy_(torch.tensor(offs, dtype=torch.int64))
+        host[8 * B:16 * B].view(torch.int32).copy_(torch.tensor([[t.shape[1], t.shape[0]] for t in images], dtype=torch.int32).reshape(-1))
+        n = buf["head"] + pos
+        buf["dev_in"][:n].copy_(host[:n], non_blocking=True)
+        buf["offs"], buf["shapes"], buf["bytes"] = offs, [tuple(t.shape) for t in images], pos
+        dev = buf["dev_in"]
+        arg = L.ImageInArgs(_ptr(dev, buf["head"]), pos, _ptr(dev), _ptr(dev, 8 * B), B, Cn, self.H, self.W, _ptr(self.inp))
+        OpList([("image_in", arg)]).run(current_stream())        # (behind the upload, on torch's current stream)
+        return self.inp
+
+    def image_out(self, x: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
+        """The images of the last image_in() batch out of `x` (default: the denoised batch -- self.pme, the network output for the MSE
+        pipelines) as bytes (SSDN_OP_IMAGE_OUT): one launch that crops to every extent, clips to [0, 1], multiplies by 255, truncates
+        and transposes back, one download.  -> B uint8 CPU tensors [h, w, C]: views of the engine's pinned buffer, overwritten by the
+        next call.  Synchronises."""
+        buf = self._img
+        if "offs" not in buf:
+            raise L.SsdnHipError("image_out: needs a preceding image_in()")
+        if x is None:
+            x = self.pme if self.pipeline == "ssdn" else self.main.tensor("out32")
+        shape = (self.B, self.C, self.H, self.W)
+        if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != shape or x.device != self.inp.device:
+            raise L.SsdnHipError("image_out: x must be a contiguous fp32 [B,C,H,W] device tensor of the engine's shape")
+        dev, n = buf["dev_in"], buf["bytes"]
+        arg = L.ImageOutArgs(_ptr(x), _ptr(dev, 8 * self.B), _ptr(dev), _ptr(buf["dev_out"]), n, *shape)
+        OpList([("image_out", arg)]).run(current_stream())
+        buf["host_out"][:n].copy_(buf["dev_out"][:n], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return [buf["host_out"][o:o + h * w * c].view(h, w, c) for o, (h, w, c) in zip(buf["offs"], buf["shapes"])]
 
     def _head_addend(self, on: bool) -> None:
         """input_grad engines: whether the first network input gradient of the sum adds the head term the VJP left in `dx`"""

@@ -1,0 +1,145 @@
+"""Time whole-image denoising for an ssdn gauss25 known-sigma RGB model with random weights over `--images` noisy
+images of 512 x 512 and of 768 x 768, one image per batch: per image, between device events (which also cover the host work in between),
+  host    -- the host route the tests compare against: to_tensor, permute, pad_to_output_size, fp32 upload, run_pipeline, fp32
+             download, unpad, tensor2image;
+  denoise -- Denoiser.denoise: packed bytes up, SSDN_OP_IMAGE_IN, the same plan, SSDN_OP_IMAGE_OUT, bytes down;
+  network -- the plan's forward list alone on the input already in place: the floor.
+Prints one JSON line.  --trace DIR: runs itself once under `rocprofv3 --kernel-trace --stats` (a child process, nothing else traced) and
+prints the times of k_image_in / k_image_out per size with their algorithmic HBM bytes (in: 1 byte read and 4 written per padded element;
+out: 4 read and 1 written per element of the extent) and the share of `--hbm-gbs` they achieve; --csv FILE also writes that table."""
+import argparse
+import csv
+import glob
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "selfsupervised-denoising_amd"), os.path.join(ROOT, "oracle")):
+    sys.path.insert(0, p)
+
+SIZES = (512, 768)
+
+
+def run(args):
+    import numpy as np
+    import torch
+    from PIL import Image
+    import ssdn
+    from ssdn.datasets import NoisyDataset
+    from ssdn.datasets.transforms import to_tensor
+    from ssdn.denoiser import Denoiser
+    from ssdn.params import ConfigValue, NoiseAlgorithm, NoiseValue, PipelineOutput
+    from ssdn.utils import tensor2image
+    cfg = ssdn.cfg.base()
+    cfg[ConfigValue.ALGORITHM] = NoiseAlgorithm.SELFSUPERVISED_DENOISING
+    cfg[ConfigValue.NOISE_STYLE] = "gauss25"
+    cfg[ConfigValue.NOISE_VALUE] = NoiseValue.KNOWN
+    torch.manual_seed(0)
+    d = Denoiser(ssdn.cfg.infer(cfg, model_only=True), device="cuda:0")
+    d.eval()
+    g = np.random.default_rng(0)
+    res = dict(images=args.images)
+    MD = NoisyDataset.Metadata
+    meta = {MD.INPUT_NOISE_VALUES: torch.full((1, 1, 1, 1), 25 / 255)}
+    nd = NoisyDataset(None, "gauss25", None, pad_multiple=32, square=True)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / args.images, (time.perf_counter() - t0) * 1e3 / args.images
+
+    for S in SIZES:
+        images = [g.integers(0, 256, size=(S, S, 3), dtype=np.uint8) for _ in range(args.images)]
+
+        def host():
+            out = []
+            for im in images:
+                x = nd.pad_to_output_size(to_tensor(Image.fromarray(im)).permute(0, 2, 1))
+                shape = torch.tensor([list(x.shape)])
+                with torch.no_grad():
+                    o = d.run_pipeline([x[None].to(d.device), torch.zeros(0), meta])[PipelineOutput.IMG_DENOISED].cpu()
+                out.append(np.asarray(tensor2image(NoisyDataset.unpad(o, {MD.IMAGE_SHAPE: shape}, 0))))
+            return out
+
+        def device():
+            return d.denoise(images, noise_param=25)["out"]
+
+        a, b = host(), device()                                   # warm-up: the plan, the pinned buffers
+        assert all(np.array_equal(x, y.numpy()) for x, y in zip(a, b)), "the two routes differ"
+        eng = d._engines[(1, S, S, False, 64)][0]
+
+        def network():
+            for _ in range(args.images):
+                eng.forward()
+        network()
+        for name, fn in (("host", host), ("denoise", device), ("network", network)):
+            ev, wall = timed(fn)
+            res["%s_%d_ms" % (name, S)] = round(ev, 3)
+            res["%s_%d_wall_ms" % (name, S)] = round(wall, 3)
+    print(json.dumps(res))
+
+
+def trace(args):
+    os.makedirs(args.trace, exist_ok=True)
+    cmd = ["timeout", "-k", "10", "400", "rocprofv3", "--kernel-trace", "--stats", "-d", args.trace, "-o", "denoise", "--output-format", "csv",
+           "--", sys.executable, os.path.abspath(__file__), "--images", str(args.images)]
+    r = subprocess.run(cmd)
+    if r.returncode != 0:
+        sys.exit("rocprofv3 run failed with exit status %d" % r.returncode)
+    traces = sorted(glob.glob(os.path.join(args.trace, "**", "*kernel_trace.csv"), recursive=True), key=os.path.getmtime)
+    if not traces:
+        sys.exit("no kernel_trace.csv under " + args.trace)
+    rows = []
+    with open(traces[-1]) as fh:
+        for row in csv.DictReader(fh):
+            name = row["Kernel_Name"]
+            name = name[5:] if name.startswith("void ") else name
+            if name.startswith("k_image_"):
+                rows.append((int(row["Start_Timestamp"]), name.split("<")[0].split("(")[0], int(row["End_Timestamp"]) - int(row["Start_Timestamp"]),
+                             row.get("VGPR_Count"), row.get("LDS_Block_Size")))
+    rows.sort()
+    per = 2 * args.images                                          # per size: the warm-up pass and the timed pass of Denoiser.denoise
+    out, table = {}, []
+    for name in ("k_image_in", "k_image_out"):
+        mine = [r for r in rows if r[1] == name]
+        if len(mine) != per * len(SIZES):
+            sys.exit("%s: %d dispatches in the trace, expected %d" % (name, len(mine), per * len(SIZES)))
+        for i, S in enumerate(SIZES):
+            dur = [r[2] for r in mine[i * per + 1:(i + 1) * per]]         # (the first launch of a size loads the code object / a cold cache)
+            nbytes = 5 * 3 * S * S
+            avg = sum(dur) / len(dur)
+            out["%s_%d" % (name, S)] = dict(calls=len(dur), avg_us=round(avg / 1e3, 2), min_us=round(min(dur) / 1e3, 2),
+                                            max_us=round(max(dur) / 1e3, 2), hbm_bytes=nbytes, gbs=round(nbytes / avg, 1),
+                                            hbm_share=round(nbytes / avg / args.hbm_gbs, 4), vgprs=mine[0][3], lds_bytes=mine[0][4])
+            table.append([name, S, len(dur), "%.1f" % avg, min(dur), max(dur), nbytes, "%.1f" % (nbytes / avg), mine[0][3], mine[0][4]])
+    if args.csv:
+        with open(args.csv, "w", newline="") as fh:
+            w = csv.writer(fh)
+            w.writerow(["Kernel", "Size", "Calls", "AverageNs", "MinNs", "MaxNs", "HbmBytes", "GBperS", "VGPR_Count", "LDS_Block_Size"])
+            w.writerows(table)
+    print(json.dumps(dict(kernel_times=out, source=os.path.basename(traces[-1]))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=20)
+    ap.add_argument("--hbm-gbs", type=float, default=6300.0, help="HBM bandwidth the achieved share is stated against, GB/s")
+    ap.add_argument("--trace", metavar="DIR", default=None, help="run once under rocprofv3 --kernel-trace --stats and summarise")
+    ap.add_argument("--csv", metavar="FILE", default=None, help="with --trace: also write the per-kernel table there")
+    args = ap.parse_args()
+    if args.trace:
+        trace(args)
+    else:
+        run(args)
+
+
+if __name__ == "__main__":
+    main()
