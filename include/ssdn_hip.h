@@ -76,7 +76,8 @@ enum ssdn_op_type {
     SSDN_OP_SSIM = 27,          /* per-sample SSIM of two image batches over each sample's un-padded extent, optional SSIM map (no planned list holds it) */
     SSDN_OP_CALIBRATION = 28,   /* per-sample calibration statistics of the posterior N(mean, cov) against the clean image, optional z histogram / z map (no planned list holds it) */
     SSDN_OP_IMAGE_IN = 29,      /* whole uint8 images of differing sizes -> the padded fp32 input batch: / 255, transposed, reflection-padded (no planned list holds it) */
-    SSDN_OP_IMAGE_OUT = 30      /* an fp32 batch -> uint8 images of differing sizes: cropped to each extent, clipped, * 255, truncated, transposed (no planned list holds it) */
+    SSDN_OP_IMAGE_OUT = 30,     /* an fp32 batch -> uint8 images of differing sizes: cropped to each extent, clipped, * 255, truncated, transposed (no planned list holds it) */
+    SSDN_OP_NOISE_EST = 31      /* a blind per-image noise-level estimate (gauss sigma, poisson lambda) from the packed uint8 images SSDN_OP_IMAGE_IN reads (no planned list holds it) */
 };
 
 /* One record of the op list.  `args` points at the matching ssdn_*_args struct (host memory).
@@ -714,6 +715,46 @@ typedef struct ssdn_image_out_args {
     int64_t dst_bytes;
     int32_t B, C, H, W;
 } ssdn_image_out_args;
+
+/* ---- SSDN_OP_NOISE_EST ---------------------------------------------------------------------------
+ * A blind noise-level estimate per image, from the packed bytes SSDN_OP_IMAGE_IN reads (src, src_bytes, offs, ext, B, C, H, W as there:
+ * image b is upright uint8 img[y][x][c] of h_b x w_b x C from byte offs[b], ext[b] = (w_b, h_b) clamped to [0,H] x [0,W]).  Nothing in
+ * the reference: every path there adds the noise itself and knows its parameter.  ssdn.utils.estimate_noise is this text in float64.
+ * Per 3x3 window, i.e. per (y, x, c) with 1 <= y <= h-2, 1 <= x <= w-2 (the channels pool into one table), in integers:
+ *     r = sum K[dy][dx] p,  K = [[1,-2,1],[-2,4,-2],[1,-2,1]]  (Immerkaer: Var r = 36 v for i.i.d. noise of variance v; planes cancel)
+ *     S = sum p;  the window is valid iff all nine bytes lie in [1, 254];  class g = (S / 9) >> 5;  bin k = min(|r|, 1023)
+ * Table: hist[b][g][k] uint32 = the count of valid windows, ssum[b][g] uint64 = the sum of S over them; n_g = sum_k hist[g][k], n = sum n_g.
+ * Grouped median of a histogram q of total N: half = N/2, k* the smallest k with cum(k) >= half, below = cum(k*-1), lo = max(k*-0.5, 0),
+ * hi = k*+0.5, med = lo + (hi-lo)(half-below)/q[k*]; NaN if k* = 1023 (the clamp bin) or N = 0.
+ * Estimates (fp64, every product, quotient and sum rounded on its own), c = 6 * 0.6744897501960817, NMIN = 256:
+ *     sigma   = max(med(sum_g hist[g]) / c, 0.5) in byte units; NaN if n < NMIN
+ *     per class with n_g >= NMIN: sigma_g = med(hist[g]) / c, m_g = ssum[g] / (9 n_g); the other classes are NaN and left out
+ *     lambda  = min(255 sum n_g m_g^2 / sum n_g m_g sigma_g^2, 260100) over the classes kept, g ascending; a zero denominator gives the
+ *               cap; NaN if no class is kept (the head's model Var = mu / lambda, in byte units 255 m / lambda)
+ * est[b] = (sigma, lambda, n, classes kept, sigma_g[8], m_g[8]).  param (may be NULL): param[b] = (float)(sigma / 255) for kind 0 (gauss),
+ * (float)lambda for kind 1 (poisson) -- the head's units; NaN stays NaN.
+ * The op zeroes hist and ssum on its stream, counts (k_noise_est: one workgroup of 1024 threads per 64 x 32 tile of window centres and
+ * sample, the tile and its one-pixel halo staged in LDS, an LDS table, integer atomics for its non-zero entries) and reduces
+ * (k_noise_est_final: one workgroup per sample): integer adds commute, so the outputs are the same bits from launch to launch.  ext and offs are device memory:
+ * a byte is read only inside [0, src_bytes), a byte outside counts as 0 and so invalidates its windows; wrong tables give a wrong
+ * estimate, never an access outside the buffers.  Argument errors are raised before any device call (text prefixed "noise_est:"): a NULL
+ * src, offs, ext, hist, ssum or est, C not 1 or 3, B, H or W < 1, a negative byte count, kind not 0 or 1, hist not 16-byte aligned,
+ * B or the tile rows ceil(W / 32) above 65535.  Adding this op changed no existing struct: the ABI version stays. */
+#define SSDN_NOISE_EST_CLASSES 8
+#define SSDN_NOISE_EST_BINS 1024
+#define SSDN_NOISE_EST_NEST 20
+typedef struct ssdn_noise_est_args {
+    const uint8_t* src;   /* packed images, device */
+    int64_t src_bytes;
+    const int64_t* offs;  /* device [B] */
+    const int32_t* ext;   /* device [B][2] = (w_b, h_b) */
+    int32_t B, C, H, W;
+    int32_t kind;         /* 0 gauss, 1 poisson: what param receives */
+    uint32_t* hist;       /* out [B][8][1024] */
+    uint64_t* ssum;       /* out [B][8] */
+    double* est;          /* out [B][20] */
+    float* param;         /* out [B], may be NULL */
+} ssdn_noise_est_args;
 
 /* ---- SSDN_OP_INPUT_GRAD --------------------------------------------------------------------
  * replaces: the data gradient autograd propagates into the network input through the first conv (noise_network.py:69-71) and the

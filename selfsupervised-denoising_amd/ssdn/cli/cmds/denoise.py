@@ -1,8 +1,9 @@
-"""`ssdn denoise --model M --input I --output O [--noise_param P] [--batch_size B] [--bucket N] [--uniform] [--std] [--recursive]`:
+"""`ssdn denoise --model M --input I --output O [--noise_param P|auto] [--batch_size B] [--bucket N] [--uniform] [--std] [--recursive]`:
 denoise already noisy images with a trained model (the reference has no such command: its evaluator takes clean datasets and adds
 the noise itself).  I: an image file or a folder of images (file discovery and channel conversion of datasets/folder.py); writes
 O/<relative stem>.png, with --std O/<relative stem>_std.npy (float32 [C,h,w] posterior std dev, ssdn models only), and O/denoise.csv
-with one row per image.  PNG decode and encode stay on the host with PIL; everything between is `Denoiser.denoise`."""
+with one row per image (with --noise_param auto also the noise parameter estimated for it).  PNG decode and encode stay on the host
+with PIL; everything between is `Denoiser.denoise`."""
 import os
 from typing import Dict, List, Tuple
 
@@ -33,7 +34,9 @@ class DenoiseCommand(Command):
         p.add_argument("--output", "-o", required=True, help="Directory the denoised PNGs and denoise.csv are written to.")
         p.add_argument("--noise_param", default=None,
                        help="The noise parameter of the images, for ssdn models trained with a known one: the numeric part of the "
-                            "noise style (gauss: an integer is /255; poisson: lambda; impulse: an integer is per cent).")
+                            "noise style (gauss: an integer is /255; poisson: lambda; impulse: an integer is per cent), or "
+                            "'auto' (gauss and poisson models): estimate it per image on the device; denoise.csv then gains a "
+                            "noise_param column with the value used.")
         p.add_argument("--batch_size", type=int, default=1, help="Images of one padded shape per batch.")
         p.add_argument("--bucket", type=int, default=None,
                        help="Pad every image to a multiple of this (a multiple of 32; default 32): fewer distinct plans for more padding.")
@@ -66,7 +69,8 @@ class DenoiseCommand(Command):
         out_dir = args["output"]
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "denoise.csv"), "w") as csv:
-            csv.write(",".join(["file", "width", "height"] + (["noise_std"] if "noise_std" in res else [])) + "\n")
+            csv.write(",".join(["file", "width", "height"] + (["noise_std"] if "noise_std" in res else [])
+                               + (["noise_param"] if "noise_param" in res else [])) + "\n")
             for k, path in enumerate(files):
                 stem = os.path.splitext(os.path.relpath(path, base))[0]
                 os.makedirs(os.path.dirname(os.path.join(out_dir, stem)) or out_dir, exist_ok=True)
@@ -75,5 +79,6 @@ class DenoiseCommand(Command):
                     np.save(os.path.join(out_dir, stem + "_std.npy"), res["std"][k].numpy().astype(np.float32))
                 h, w = images[k].shape[:2]
                 csv.write(",".join([os.path.relpath(path, base), str(w), str(h)]
-                                   + (["{:.6f}".format(res["noise_std"][k])] if "noise_std" in res else [])) + "\n")
+                                   + (["{:.6f}".format(res["noise_std"][k])] if "noise_std" in res else [])
+                                   + (["{:.9g}".format(res["noise_param"][k])] if "noise_param" in res else [])) + "\n")
         return res

@@ -39,6 +39,7 @@ reference image, the noise metadata or the std-dev outputs.
 """
 from __future__ import annotations
 
+import math
 import weakref
 from typing import Dict, List, Optional, Tuple
 
@@ -316,7 +317,9 @@ class Denoiser(nn.Module):
                 # `_ssdn_const`); that very OBJECT (held by reference, so its address cannot be handed out again) is uploaded once.
                 # Everything else -- e.g. the per-minibatch tensor of a ranged style, filled through a raw pointer, whose
                 # (address, _version) can repeat with different contents -- is copied every step (B floats, device to device).
-                if not (getattr(npv, "_ssdn_const", False) and npv is getattr(eng, "_np_src", None)):
+                if npv.data_ptr() == eng.noise_param.data_ptr():       # (denoise's "auto": the estimator has written the engine's tensor itself)
+                    eng._np_src = None
+                elif not (getattr(npv, "_ssdn_const", False) and npv is getattr(eng, "_np_src", None)):
                     eng.noise_param.copy_(npv.reshape(B).to(torch.float32), non_blocking=True)
                     eng._np_src = npv if getattr(npv, "_ssdn_const", False) else None
         else:
@@ -393,7 +396,8 @@ class Denoiser(nn.Module):
     def _noise_param_value(self, noise_param) -> Optional[float]:
         """`denoise`'s noise_param as the value Metadata.INPUT_NOISE_VALUES carries: the numeric part of the model's noise style in
         the style grammar (ssdn.utils.noise.parse_style) -- gauss: an integer is /255; poisson: lambda; impulse: an integer is per
-        cent.  Required for a known-noise SSDN model and refused for every other one (ValueError)."""
+        cent.  Required for a known-noise SSDN model and refused for every other one (ValueError).  "auto" (gauss and poisson models
+        only: there is no estimator for impulse noise) comes back as it is: `denoise` then estimates the value per image on the device."""
         from ssdn.utils import noise
         known = self._pipeline == Pipeline.SSDN and self.cfg[ConfigValue.NOISE_VALUE] == NoiseValue.KNOWN
         if not known:
@@ -403,6 +407,11 @@ class Denoiser(nn.Module):
         if noise_param is None:
             raise ValueError("denoise: this model was trained with a known noise parameter: noise_param is required")
         kind = noise.parse_style(self.cfg[ConfigValue.NOISE_STYLE])[0]
+        if isinstance(noise_param, str) and noise_param.strip().lower() == "auto":
+            if kind not in ("gauss", "poisson"):
+                raise ValueError("denoise: noise_param 'auto' needs a noise-level estimator and no estimator exists for %s noise: "
+                                 "pass the number" % kind)
+            return "auto"
         try:
             params = noise.parse_style(kind + str(noise_param).strip())[1]
         except (ValueError, IndexError):
@@ -418,34 +427,10 @@ class Denoiser(nn.Module):
             return noise.impulse_alpha(v)
         return float(v)
 
-    def denoise(self, images: List, noise_param=None, batch_size: int = 1, bucket: Optional[int] = None, uniform: bool = False,
-                std: bool = False) -> Dict:
-        """Denoise already noisy images.  images: uint8 arrays or tensors [h, w] or [h, w, C], upright as PIL hands them out, of any and
-        differing sizes, C the model's channel count.  Every image is reflection-padded bottom and right to a multiple of `bucket`
-        (default and unit: NoiseNetwork.input_wh_mul(); larger values trade padding for fewer distinct plans -- at most _MAX_ENGINES are
-        cached and one owns ~1 GB), to a square for a blind-spot model, with uniform=True to the largest image of the call (the
-        evaluator's pad_uniform); images of one padded shape run in batches of at most `batch_size`, a short last batch at its own size.
-        Per batch: one pinned upload of the packed bytes, SSDN_OP_IMAGE_IN (/ 255, transpose, pad), an inference run under no_grad
-        whatever the module's mode, SSDN_OP_IMAGE_OUT (crop, clip, * 255, truncate, transpose), one download (csrc/image_io.hip, DESIGN.md
-        section 3.16): the bytes `tensor2image` would give for the un-padded IMG_DENOISED of the same run.
-        noise_param: required for an ssdn model with a known noise parameter, refused (ValueError, before any device work) for every
-        other model; the numeric part of the noise style -- gauss: an integer is /255, poisson: lambda, impulse: an integer is per cent.
-        -> {"out": uint8 CPU tensors of the inputs' shapes, in input order}; ssdn models also "noise_std": per image the mean of
-        NOISE_STD_DEV over its extent; std=True (ssdn only) adds "std": float32 [C, h, w] upright posterior std maps (Denoiser.posterior's).
-        Like `posterior` it never becomes the forward that backward() / optimizer_step() / accumulate_metrics() act on."""
+    def _denoise_images(self, images: List) -> List[Tensor]:
+        """`denoise`'s images as contiguous uint8 CPU tensors [h, w, C] of the model's channel count (ValueError otherwise)"""
         import numpy as np
         Cn = self.cfg[ConfigValue.IMAGE_CHANNELS]
-        ssdn_pipe = self._pipeline == Pipeline.SSDN
-        value = self._noise_param_value(noise_param)
-        if std and not ssdn_pipe:
-            raise ValueError("denoise: std=True needs a posterior: the %s pipeline has none (ssdn models only)" % self._pipeline.value)
-        mul = NoiseNetwork.input_wh_mul()
-        bucket = mul if bucket is None else int(bucket)
-        if bucket < mul or bucket % mul:
-            raise ValueError("denoise: bucket must be a positive multiple of %d, got %d" % (mul, bucket))
-        batch_size = int(batch_size)
-        if batch_size < 1:
-            raise ValueError("denoise: batch_size must be at least 1")
         imgs = []
         for k, im in enumerate(images):
             t = im
@@ -461,14 +446,22 @@ class Denoiser(nn.Module):
             if t.shape[0] < 1 or t.shape[1] < 1:
                 raise ValueError("denoise: image %d is empty" % k)
             imgs.append(t)
-        res: Dict = {"out": [None] * len(imgs)}
-        if ssdn_pipe:
-            res["noise_std"] = [None] * len(imgs)
-        if std:
-            res["std"] = [None] * len(imgs)
-        if not imgs:
-            return res
-        # padded shapes on tensor axes 2 and 3 = along the image's x and y (NoisyDataset.get_output_size: uniform, multiple, square)
+        return imgs
+
+    @staticmethod
+    def _denoise_options(bucket: Optional[int], batch_size: int) -> Tuple[int, int]:
+        mul = NoiseNetwork.input_wh_mul()
+        bucket = mul if bucket is None else int(bucket)
+        if bucket < mul or bucket % mul:
+            raise ValueError("denoise: bucket must be a positive multiple of %d, got %d" % (mul, bucket))
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError("denoise: batch_size must be at least 1")
+        return bucket, batch_size
+
+    def _denoise_groups(self, imgs: List[Tensor], bucket: int, uniform: bool) -> Dict[Tuple[int, int], List[int]]:
+        """the images' indices by padded shape on tensor axes 2 and 3 = along the image's x and y (NoisyDataset.get_output_size: uniform,
+        multiple, square)"""
         big = (max(t.shape[1] for t in imgs), max(t.shape[0] for t in imgs))
         groups: Dict[Tuple[int, int], List[int]] = {}
         for k, t in enumerate(imgs):
@@ -476,6 +469,84 @@ class Denoiser(nn.Module):
             if self.cfg[ConfigValue.BLINDSPOT]:
                 H = W = max(H, W)
             groups.setdefault((H, W), []).append(k)
+        return groups
+
+    def estimate_noise(self, images: List, kind: Optional[str] = None, batch_size: int = 1, bucket: Optional[int] = None,
+                       uniform: bool = False) -> List[Dict]:
+        """A blind estimate of the noise level of every image, on the device (SSDN_OP_NOISE_EST, csrc/noise_est.hip, DESIGN.md section
+        3.17; ssdn.utils.estimate_noise is the definition and documents the values).  images, batch_size, bucket, uniform: as for
+        `denoise`, whose validation and grouping it shares -- an image only has to fit the engine it is uploaded to.  kind: "gauss" or
+        "poisson", default the model's noise style; an impulse model needs it given (ValueError), there is no impulse estimator.
+        -> per image {"sigma" (byte units), "lambda", "n", "classes_used", "nlf_sigma" [8], "nlf_mean" [8]} and "noise_param": the
+        fp32 value of `kind` in the head's units (sigma / 255 or lambda) as a float, NaN for an image with fewer than 256 valid
+        windows.  Runs no network and leaves training state and the last forward alone."""
+        from ssdn.utils import noise
+        if kind is None:
+            kind = noise.parse_style(self.cfg.get(ConfigValue.NOISE_STYLE) or "gauss")[0]
+            if kind not in ("gauss", "poisson"):
+                raise ValueError("estimate_noise: no estimator exists for %s noise: pass kind='gauss' or 'poisson'" % kind)
+        if kind not in ("gauss", "poisson"):
+            raise ValueError("estimate_noise: kind must be 'gauss' or 'poisson', got %r" % (kind,))
+        bucket, batch_size = self._denoise_options(bucket, batch_size)
+        imgs = self._denoise_images(images)
+        res: List = [None] * len(imgs)
+        if not imgs:
+            return res
+        with torch.no_grad():
+            for (H, W), members in self._denoise_groups(imgs, bucket, uniform).items():
+                for lo in range(0, len(members), batch_size):
+                    idx = members[lo:lo + batch_size]
+                    eng = self._engine(len(idx), H, W, False)
+                    eng.image_in([imgs[k] for k in idx])
+                    est = eng.estimate_noise(kind).cpu()             # (synchronises)
+                    par = eng._img["est_param"].cpu()
+                    for b, k in enumerate(idx):
+                        res[k] = self._noise_est_dict(est[b], float(par[b]))
+        return res
+
+    @staticmethod
+    def _noise_est_dict(row: Tensor, param: float) -> Dict:
+        """one row of SSDN_OP_NOISE_EST's `est` (host float64 [20]) as ssdn.utils.estimate_noise's dict, plus the fp32 parameter"""
+        return {"sigma": float(row[0]), "lambda": float(row[1]), "n": int(row[2]), "classes_used": int(row[3]),
+                "nlf_sigma": row[4:12].clone(), "nlf_mean": row[12:20].clone(), "noise_param": param}
+
+    def denoise(self, images: List, noise_param=None, batch_size: int = 1, bucket: Optional[int] = None, uniform: bool = False,
+                std: bool = False) -> Dict:
+        """Denoise already noisy images.  images: uint8 arrays or tensors [h, w] or [h, w, C], upright as PIL hands them out, of any and
+        differing sizes, C the model's channel count.  Every image is reflection-padded bottom and right to a multiple of `bucket`
+        (default and unit: NoiseNetwork.input_wh_mul(); larger values trade padding for fewer distinct plans -- at most _MAX_ENGINES are
+        cached and one owns ~1 GB), to a square for a blind-spot model, with uniform=True to the largest image of the call (the
+        evaluator's pad_uniform); images of one padded shape run in batches of at most `batch_size`, a short last batch at its own size.
+        Per batch: one pinned upload of the packed bytes, SSDN_OP_IMAGE_IN (/ 255, transpose, pad), an inference run under no_grad
+        whatever the module's mode, SSDN_OP_IMAGE_OUT (crop, clip, * 255, truncate, transpose), one download (csrc/image_io.hip, DESIGN.md
+        section 3.16): the bytes `tensor2image` would give for the un-padded IMG_DENOISED of the same run.
+        noise_param: required for an ssdn model with a known noise parameter, refused (ValueError, before any device work) for every
+        other model; the numeric part of the noise style -- gauss: an integer is /255, poisson: lambda, impulse: an integer is per cent.
+        "auto" (known gauss and poisson models; an impulse model refuses it: there is no estimator for impulse noise) estimates it per
+        image on the device between SSDN_OP_IMAGE_IN and the run (`estimate_noise`) and adds "noise_param": the fp32 value used per
+        image; an image too small or too saturated for an estimate raises ValueError naming its index.
+        -> {"out": uint8 CPU tensors of the inputs' shapes, in input order}; ssdn models also "noise_std": per image the mean of
+        NOISE_STD_DEV over its extent; std=True (ssdn only) adds "std": float32 [C, h, w] upright posterior std maps (Denoiser.posterior's).
+        Like `posterior` it never becomes the forward that backward() / optimizer_step() / accumulate_metrics() act on."""
+        ssdn_pipe = self._pipeline == Pipeline.SSDN
+        value = self._noise_param_value(noise_param)
+        if std and not ssdn_pipe:
+            raise ValueError("denoise: std=True needs a posterior: the %s pipeline has none (ssdn models only)" % self._pipeline.value)
+        bucket, batch_size = self._denoise_options(bucket, batch_size)
+        imgs = self._denoise_images(images)
+        auto = isinstance(value, str)                    # "auto": the value is estimated per image on the device
+        res: Dict = {"out": [None] * len(imgs)}
+        if auto:
+            from ssdn.utils import noise
+            kind = noise.parse_style(self.cfg[ConfigValue.NOISE_STYLE])[0]
+            res["noise_param"] = [None] * len(imgs)
+        if ssdn_pipe:
+            res["noise_std"] = [None] * len(imgs)
+        if std:
+            res["std"] = [None] * len(imgs)
+        if not imgs:
+            return res
+        groups = self._denoise_groups(imgs, bucket, uniform)
         keep = (self._last_engine, getattr(self, "_has_loss_last", None))
         try:
             with torch.no_grad():
@@ -485,10 +556,21 @@ class Denoiser(nn.Module):
                         B = len(idx)
                         eng = self._engine(B, H, W, False)
                         data = [eng.image_in([imgs[k] for k in idx])]
-                        if value is not None:
+                        if auto:
+                            # the estimates land in the engine's parameter tensor, which _run takes as it is: no host round trip
+                            eng.estimate_noise(kind, into_noise_param=True)
+                            data += [torch.zeros(0), {NoisyDataset.Metadata.INPUT_NOISE_VALUES: eng.noise_param}]
+                        elif value is not None:
                             data += [torch.zeros(0), {NoisyDataset.Metadata.INPUT_NOISE_VALUES: torch.full((B, 1, 1, 1), value)}]
                         self._run(data, clone=False)         # (no_grad: the inference plan of this shape, whose input is already in place)
                         outs = eng.image_out()
+                        if auto:                             # (image_out has synchronised)
+                            used = eng.noise_param.cpu()
+                            for b, k in enumerate(idx):
+                                if not math.isfinite(float(used[b])):
+                                    raise ValueError("denoise: image %d has too few valid 3x3 windows for a noise estimate (it is smaller "
+                                                     "than 3x3 or saturated): pass noise_param as a number" % k)
+                                res["noise_param"][k] = float(used[b])
                         smap = eng.posterior(cov=False, std=True)["std"].cpu() if std else None
                         nstd = (eng.noise_std if eng.style == "poisson" else eng.noise_std.cpu()) if ssdn_pipe else None
                         for b, k in enumerate(idx):

@@ -357,7 +357,7 @@ class DenoiserEngine:
         self._post = {}             # posterior(): cov / std / samples buffers, allocated on first use (no plan tensor)
         self._ssim = {}             # ssim(): value / map / scratch buffers, allocated on first use (no plan tensor)
         self._calib = {}            # calibration(): stats / hist / zmap / scratch buffers, allocated on first use (no plan tensor)
-        self._img = {}              # image_in() / image_out(): pinned and device byte buffers with their tables, allocated on first use (no plan tensor)
+        self._img = {}              # image_in() / image_out() / estimate_noise(): pinned and device byte buffers with their tables, allocated on first use (no plan tensor)
 
     # ---- op construction -----------------------------------------------------------------------------------
     def _gmax(self, net: Optional[DeviceNet]):
@@ -759,6 +759,31 @@ class DenoiserEngine:
         buf["host_out"][:n].copy_(buf["dev_out"][:n], non_blocking=True)
         torch.cuda.current_stream().synchronize()
         return [buf["host_out"][o:o + h * w * c].view(h, w, c) for o, (h, w, c) in zip(buf["offs"], buf["shapes"])]
+
+    def estimate_noise(self, kind: str, into_noise_param: bool = False) -> torch.Tensor:
+        """A blind noise-level estimate of every image of the last image_in() batch (SSDN_OP_NOISE_EST, csrc/noise_est.hip) from the
+        bytes and tables still on the device.  kind: "gauss" or "poisson" -- what the fp32 parameter in the head's units is (sigma / 255
+        or lambda).  into_noise_param: write that parameter into `self.noise_param`, where the head of the next run reads it, without a
+        host round trip.  -> the device fp64 tensor [B, 20] (sigma, lambda, n, classes kept, sigma_g[8], m_g[8]; ssdn.utils.estimate_noise
+        is the definition), overwritten by the next call; the fp32 parameters [B] are in `self.noise_param` or, without into_noise_param, in
+        `self._img["est_param"]`.  Does not synchronise."""
+        buf = self._img
+        if "offs" not in buf:
+            raise L.SsdnHipError("estimate_noise: needs a preceding image_in()")
+        if kind not in L.NOISE_EST_KIND:
+            raise L.SsdnHipError("estimate_noise: kind must be gauss or poisson, got %r" % (kind,))
+        B = self.B
+        if "est" not in buf:
+            buf["est_hist"] = torch.zeros((B, L.NOISE_EST_CLASSES, L.NOISE_EST_BINS), dtype=torch.int32, device=self.device)
+            buf["est_ssum"] = torch.zeros((B, L.NOISE_EST_CLASSES), dtype=torch.int64, device=self.device)
+            buf["est"] = torch.zeros((B, L.NOISE_EST_NEST), dtype=torch.float64, device=self.device)
+            buf["est_param"] = torch.zeros((B,), dtype=torch.float32, device=self.device)
+        dev = buf["dev_in"]
+        par = self.noise_param if into_noise_param else buf["est_param"]
+        arg = L.NoiseEstArgs(_ptr(dev, buf["head"]), buf["bytes"], _ptr(dev), _ptr(dev, 8 * B), B, self.C, self.H, self.W,
+                             L.NOISE_EST_KIND[kind], _ptr(buf["est_hist"]), _ptr(buf["est_ssum"]), _ptr(buf["est"]), _ptr(par))
+        OpList([("noise_est", arg)]).run(current_stream())       # (behind image_in()'s upload, on torch's current stream)
+        return buf["est"]
 
     def _head_addend(self, on: bool) -> None:
         """input_grad engines: whether the first network input gradient of the sum adds the head term the VJP left in `dx`"""

@@ -17,7 +17,7 @@ MAX_TAPS = 9
 OP = dict(pack_input=1, conv=2, pool_fwd=3, pool_bwd=4, upsum_bwd=5, unrot_fwd=6, unrot_bwd=7, wgrad=8, wreduce=9,
           wpack=10, grad_pack=11, head_ssdn=12, head_final=13, spatial_mean=14, mse=15, mask_mse=16, adam=17,
           metrics=18, zero=19, event_record=20, noise=21, input_grad=22, head_vjp=23,
-          mse_vjp=24, accum=25, head_posterior=26, ssim=27, calibration=28, image_in=29, image_out=30)
+          mse_vjp=24, accum=25, head_posterior=26, ssim=27, calibration=28, image_in=29, image_out=30, noise_est=31)
 
 i32, f32, vp = C.c_int32, C.c_float, C.c_void_p
 
@@ -188,12 +188,22 @@ class ImageOutArgs(C.Structure):
                 ("W", i32)]
 
 
+class NoiseEstArgs(C.Structure):
+    _fields_ = [("src", vp), ("src_bytes", C.c_int64), ("offs", vp), ("ext", vp), ("B", i32), ("C", i32), ("H", i32), ("W", i32),
+                ("kind", i32), ("hist", vp), ("ssum", vp), ("est", vp), ("param", vp)]
+
+
+NOISE_EST_CLASSES, NOISE_EST_BINS, NOISE_EST_NEST = 8, 1024, 20        # SSDN_NOISE_EST_* of include/ssdn_hip.h
+NOISE_EST_KIND = dict(gauss=0, poisson=1)
+
+
 ARG_TYPES = dict(pack_input=PackInputArgs, conv=ConvArgs, pool_fwd=PoolArgs, pool_bwd=PoolArgs, upsum_bwd=UpsumArgs,
                  unrot_fwd=UnrotArgs, unrot_bwd=UnrotArgs, wgrad=WgradArgs, wreduce=WreduceArgs, wpack=WpackArgs,
                  grad_pack=GradPackArgs, head_ssdn=HeadArgs, head_final=HeadFinalArgs, spatial_mean=SpatialMeanArgs,
                  mse=MseArgs, mask_mse=MseArgs, adam=AdamArgs, metrics=MetricsArgs, zero=ZeroArgs, event_record=EventArgs, noise=NoiseArgs,
                  input_grad=InputGradArgs, head_vjp=HeadVjpArgs, mse_vjp=MseVjpArgs, accum=AccumArgs,
-                 head_posterior=HeadPosteriorArgs, ssim=SsimArgs, calibration=CalibrationArgs, image_in=ImageInArgs, image_out=ImageOutArgs)
+                 head_posterior=HeadPosteriorArgs, ssim=SsimArgs, calibration=CalibrationArgs, image_in=ImageInArgs, image_out=ImageOutArgs,
+                 noise_est=NoiseEstArgs)
 
 # every symbol include/ssdn_hip.h declares
 ABI_VERSION = 19      # SSDN_ABI_VERSION of include/ssdn_hip.h this binding mirrors

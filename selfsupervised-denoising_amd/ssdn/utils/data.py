@@ -193,6 +193,109 @@ def calculate_calibration(mean: Tensor, cov: Tensor, ref: Tensor, hist: bool = F
     return res
 
 
+# ---- blind noise-level estimation (SSDN_OP_NOISE_EST, csrc/noise_est.hip) -------------------------------------------------------
+NOISE_EST_CLASSES, NOISE_EST_BINS, NOISE_EST_NMIN = 8, 1024, 256
+NOISE_EST_C = 6 * 0.6744897501960817             # |r| has standard deviation 6 sigma; the median of |N(0, 1)| is 0.6744...
+NOISE_EST_SIGMA_FLOOR, NOISE_EST_LAMBDA_CAP = 0.5, 260100.0
+
+
+def _grouped_median(q: Tensor) -> Tensor:
+    """Grouped medians of the histograms q [..., 1024] (int64) -> float64 [...]: half = N/2, k* the smallest bin with cum(k*) >= half,
+    med = lo + (hi - lo)(half - cum(k* - 1)) / q[k*] on the bin's edges lo = max(k* - 0.5, 0), hi = k* + 0.5; NaN for N = 0 or for
+    k* = 1023, the clamp bin."""
+    cum = q.cumsum(-1)
+    N = cum[..., -1:]
+    k = ((2 * cum >= N).to(torch.int64).cumsum(-1) == 0).sum(-1, keepdim=True).clamp(max=q.shape[-1] - 1)    # the first bin that reaches half
+    qk = q.gather(-1, k)
+    below = cum.gather(-1, k) - qk
+    half = N.to(torch.float64) / 2.0
+    kf = k.to(torch.float64)
+    lo, hi = torch.clamp(kf - 0.5, min=0.0), kf + 0.5
+    med = lo + ((hi - lo) * (half - below.to(torch.float64))) / qk.to(torch.float64)
+    nan = torch.full_like(med, float("nan"))
+    return torch.where((N > 0) & (k < q.shape[-1] - 1), med, nan)[..., 0]
+
+
+def noise_estimates(hist: Tensor, ssum: Tensor) -> Dict:
+    """The estimates of `estimate_noise` from one image's integer table (hist int64 [8,1024], ssum int64 [8]), float64 on their device."""
+    f64 = torch.float64
+    hist, ssum = hist.to(torch.int64), ssum.to(torch.int64)
+    nan = torch.full((), float("nan"), dtype=f64, device=hist.device)
+    ng = hist.sum(1)
+    n = int(ng.sum())
+    sigma = nan
+    if n >= NOISE_EST_NMIN:
+        sigma = _grouped_median(hist.sum(0)) / NOISE_EST_C
+        sigma = torch.where(sigma < NOISE_EST_SIGMA_FLOOR, torch.full_like(sigma, NOISE_EST_SIGMA_FLOOR), sigma)      # (NaN stays NaN)
+    keep = ng >= NOISE_EST_NMIN
+    nanv = torch.full((NOISE_EST_CLASSES,), float("nan"), dtype=f64, device=hist.device)
+    sg = torch.where(keep, _grouped_median(hist) / NOISE_EST_C, nanv)
+    mg = torch.where(keep, ssum.to(f64) / (9.0 * ng.to(f64)), nanv)
+    num = den = torch.zeros((), dtype=f64, device=hist.device)
+    used = 0
+    for g in range(NOISE_EST_CLASSES):              # a least-squares fit of sigma_g^2 = 255 m_g / lambda through the origin, g ascending
+        if bool(keep[g]):
+            nm = ng[g].to(f64) * mg[g]
+            num = num + nm * mg[g]
+            den = den + nm * (sg[g] * sg[g])
+            used += 1
+    lam = nan
+    if used:
+        cap = torch.full((), NOISE_EST_LAMBDA_CAP, dtype=f64, device=hist.device)
+        lam = cap if float(den) == 0.0 else (255.0 * num) / den
+        lam = torch.where(lam > cap, cap, lam)                                                                         # (NaN stays NaN)
+    return {"sigma": float(sigma), "lambda": float(lam), "n": n, "classes_used": used, "nlf_sigma": sg.cpu(), "nlf_mean": mg.cpu()}
+
+
+def estimate_noise(image_u8, hist: bool = False) -> Dict:
+    """A blind estimate of the noise level of one image -- the specification SSDN_OP_NOISE_EST (csrc/noise_est.hip) is held to: exact
+    integers for the table, float64 after it, on the image's device.  image_u8: an upright uint8 array or tensor [h, w] or [h, w, C].
+    Per 3x3 window, i.e. per (y, x, c) with 1 <= y <= h-2 and 1 <= x <= w-2 (the channels pool into one table):
+        r = sum K p with K = [[1,-2,1],[-2,4,-2],[1,-2,1]] (Immerkaer 1996: for i.i.d. noise of variance v, Var r = 36 v, and locally
+        planar image content cancels), S = sum p; the window is valid iff all nine bytes lie in [1, 254] (0 and 255 may be clipped
+        values); intensity class g = (S // 9) >> 5; bin k = min(|r|, 1023).
+    hist[g][k] counts the valid windows, ssum[g] adds their S; n_g and n are the counts per class and in all.  With the grouped median
+    med(.) of a histogram (NaN in the clamp bin), c = 6 * 0.6744897501960817 and NMIN = 256:
+        sigma  = max(med(sum_g hist[g]) / c, 0.5), in byte units (the 25 of gauss25); NaN if n < NMIN
+        for every class with n_g >= NMIN: nlf_sigma[g] = med(hist[g]) / c, nlf_mean[g] = ssum[g] / (9 n_g); other classes NaN, left out
+        lambda = min(255 sum n_g m_g^2 / sum n_g m_g sigma_g^2, 260100) over the classes kept (the Poisson head's Var = mu / lambda, in
+                 byte units 255 m / lambda); a zero denominator gives the cap; NaN if no class is kept.
+    The floors give a noise-free picture a finite positive parameter.  Biases measured on synthetic pictures: DESIGN.md section 3.17.
+    -> {"sigma", "lambda": floats, "n", "classes_used": ints, "nlf_sigma", "nlf_mean": float64 [8]}; hist=True adds "hist" int64
+    [8,1024] and "ssum" int64 [8]."""
+    import numpy as np
+    t = image_u8
+    if isinstance(t, np.ndarray):
+        t = torch.from_numpy(np.ascontiguousarray(t))
+    if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() not in (2, 3):
+        raise ValueError("estimate_noise: a uint8 array or tensor [h, w] or [h, w, C]")
+    p = (t.unsqueeze(-1) if t.dim() == 2 else t).to(torch.int64)
+    h, w, C = p.shape
+    table = torch.zeros((NOISE_EST_CLASSES * NOISE_EST_BINS,), dtype=torch.int64, device=p.device)
+    ssum = torch.zeros((NOISE_EST_CLASSES,), dtype=torch.int64, device=p.device)
+    if h >= 3 and w >= 3:
+        K = ((1, -2, 1), (-2, 4, -2), (1, -2, 1))
+        r = torch.zeros((h - 2, w - 2, C), dtype=torch.int64, device=p.device)
+        S = torch.zeros_like(r)
+        valid = torch.ones_like(r, dtype=torch.bool)
+        for dy in range(3):
+            for dx in range(3):
+                v = p[dy:h - 2 + dy, dx:w - 2 + dx]
+                r += K[dy][dx] * v
+                S += v
+                valid &= (v >= 1) & (v <= 254)
+        g = torch.div(S, 9, rounding_mode="floor") >> 5
+        k = r.abs().clamp(max=NOISE_EST_BINS - 1)
+        one = valid.to(torch.int64).reshape(-1)
+        table.scatter_add_(0, (g * NOISE_EST_BINS + k).reshape(-1), one)
+        ssum.scatter_add_(0, g.reshape(-1), S.reshape(-1) * one)
+    table = table.view(NOISE_EST_CLASSES, NOISE_EST_BINS)
+    res = noise_estimates(table, ssum)
+    if hist:
+        res["hist"], res["ssum"] = table, ssum
+    return res
+
+
 # ---- image I/O helpers of the trainer / evaluator (utils/data.py:69-125) ------------------------------------------------------
 def tensor2image(img: Tensor):
     """CHW float tensor in [0,1] -> PIL image.  The dataset classes hand out tensors with H and W SWAPPED (PIL data

@@ -4,9 +4,12 @@ images of 512 x 512 and of 768 x 768, one image per batch: per image, between de
              download, unpad, tensor2image;
   denoise -- Denoiser.denoise: packed bytes up, SSDN_OP_IMAGE_IN, the same plan, SSDN_OP_IMAGE_OUT, bytes down;
   network -- the plan's forward list alone on the input already in place: the floor.
+--auto adds the estimator's leg: after those three, Denoiser.denoise with the number and with noise_param="auto"
+(SSDN_OP_NOISE_EST between SSDN_OP_IMAGE_IN and the run) alternate twice; `denoise_alt_*` and `auto_*` are the lists of both.
 Prints one JSON line.  --trace DIR: runs itself once under `rocprofv3 --kernel-trace --stats` (a child process, nothing else traced) and
 prints the times of k_image_in / k_image_out per size with their algorithmic HBM bytes (in: 1 byte read and 4 written per padded element;
-out: 4 read and 1 written per element of the extent) and the share of `--hbm-gbs` they achieve; --csv FILE also writes that table."""
+out: 4 read and 1 written per element of the extent; with --auto also k_noise_est: 1 byte read per element, and k_noise_est_final: the
+32 KiB table) and the share of `--hbm-gbs` they achieve; --csv FILE also writes that table."""
 import argparse
 import csv
 import glob
@@ -84,13 +87,24 @@ def run(args):
             ev, wall = timed(fn)
             res["%s_%d_ms" % (name, S)] = round(ev, 3)
             res["%s_%d_wall_ms" % (name, S)] = round(wall, 3)
+        if args.auto:
+            def auto():
+                return d.denoise(images, noise_param="auto")
+
+            used = auto()["noise_param"]                             # warm-up: the estimator's buffers
+            res["auto_param_%d" % S] = [round(min(used) * 255, 3), round(max(used) * 255, 3)]
+            for _ in range(2):
+                for name, fn in (("denoise_alt", device), ("auto", auto)):
+                    ev, wall = timed(fn)
+                    res.setdefault("%s_%d_ms" % (name, S), []).append(round(ev, 3))
+                    res.setdefault("%s_%d_wall_ms" % (name, S), []).append(round(wall, 3))
     print(json.dumps(res))
 
 
 def trace(args):
     os.makedirs(args.trace, exist_ok=True)
     cmd = ["timeout", "-k", "10", "400", "rocprofv3", "--kernel-trace", "--stats", "-d", args.trace, "-o", "denoise", "--output-format", "csv",
-           "--", sys.executable, os.path.abspath(__file__), "--images", str(args.images)]
+           "--", sys.executable, os.path.abspath(__file__), "--images", str(args.images)] + (["--auto"] if args.auto else [])
     r = subprocess.run(cmd)
     if r.returncode != 0:
         sys.exit("rocprofv3 run failed with exit status %d" % r.returncode)
@@ -102,19 +116,23 @@ def trace(args):
         for row in csv.DictReader(fh):
             name = row["Kernel_Name"]
             name = name[5:] if name.startswith("void ") else name
-            if name.startswith("k_image_"):
+            if name.startswith("k_image_") or name.startswith("k_noise_est"):
                 rows.append((int(row["Start_Timestamp"]), name.split("<")[0].split("(")[0], int(row["End_Timestamp"]) - int(row["Start_Timestamp"]),
                              row.get("VGPR_Count"), row.get("LDS_Block_Size")))
     rows.sort()
-    per = 2 * args.images                                          # per size: the warm-up pass and the timed pass of Denoiser.denoise
+    # passes of Denoiser.denoise per size: the warm-up and the timed one; with --auto the estimator's warm-up and two alternations more
+    passes = {"k_image_in": 7 if args.auto else 2, "k_image_out": 7 if args.auto else 2}
+    if args.auto:
+        passes.update(k_noise_est=3, k_noise_est_final=3)
     out, table = {}, []
-    for name in ("k_image_in", "k_image_out"):
+    for name, n in passes.items():
+        per = n * args.images
         mine = [r for r in rows if r[1] == name]
         if len(mine) != per * len(SIZES):
             sys.exit("%s: %d dispatches in the trace, expected %d" % (name, len(mine), per * len(SIZES)))
         for i, S in enumerate(SIZES):
             dur = [r[2] for r in mine[i * per + 1:(i + 1) * per]]         # (the first launch of a size loads the code object / a cold cache)
-            nbytes = 5 * 3 * S * S
+            nbytes = {"k_noise_est": 3 * S * S, "k_noise_est_final": 8 * 1024 * 4 + 8 * 8 + 20 * 8 + 4}.get(name, 5 * 3 * S * S)
             avg = sum(dur) / len(dur)
             out["%s_%d" % (name, S)] = dict(calls=len(dur), avg_us=round(avg / 1e3, 2), min_us=round(min(dur) / 1e3, 2),
                                             max_us=round(max(dur) / 1e3, 2), hbm_bytes=nbytes, gbs=round(nbytes / avg, 1),
@@ -132,6 +150,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=20)
     ap.add_argument("--hbm-gbs", type=float, default=6300.0, help="HBM bandwidth the achieved share is stated against, GB/s")
+    ap.add_argument("--auto", action="store_true", help="also time Denoiser.denoise(noise_param='auto'), alternating with the number")
     ap.add_argument("--trace", metavar="DIR", default=None, help="run once under rocprofv3 --kernel-trace --stats and summarise")
     ap.add_argument("--csv", metavar="FILE", default=None, help="with --trace: also write the per-kernel table there")
     args = ap.parse_args()
