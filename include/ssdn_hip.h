@@ -77,7 +77,9 @@ enum ssdn_op_type {
     SSDN_OP_CALIBRATION = 28,   /* per-sample calibration statistics of the posterior N(mean, cov) against the clean image, optional z histogram / z map (no planned list holds it) */
     SSDN_OP_IMAGE_IN = 29,      /* whole uint8 images of differing sizes -> the padded fp32 input batch: / 255, transposed, reflection-padded (no planned list holds it) */
     SSDN_OP_IMAGE_OUT = 30,     /* an fp32 batch -> uint8 images of differing sizes: cropped to each extent, clipped, * 255, truncated, transposed (no planned list holds it) */
-    SSDN_OP_NOISE_EST = 31      /* a blind per-image noise-level estimate (gauss sigma, poisson lambda) from the packed uint8 images SSDN_OP_IMAGE_IN reads (no planned list holds it) */
+    SSDN_OP_NOISE_EST = 31,     /* a blind per-image noise-level estimate (gauss sigma, poisson lambda) from the packed uint8 images SSDN_OP_IMAGE_IN reads (no planned list holds it) */
+    SSDN_OP_TILE_IN = 32,       /* one uint8 image of any size -> a batch of its fixed-size overlapping tiles: / 255, transposed, reflected beyond the image (no planned list holds it) */
+    SSDN_OP_TILE_OUT = 33       /* the fp32 tiles of one image -> that image, blended across the overlaps: bytes or upright fp32 planes (no planned list holds it) */
 };
 
 /* One record of the op list.  `args` points at the matching ssdn_*_args struct (host memory).
@@ -755,6 +757,58 @@ typedef struct ssdn_noise_est_args {
     double* est;          /* out [B][20] */
     float* param;         /* out [B], may be NULL */
 } ssdn_noise_est_args;
+
+/* ---- SSDN_OP_TILE_IN / SSDN_OP_TILE_OUT -----------------------------------------------------------
+ * One image of any size through a network of ONE fixed input shape: the image is cut into overlapping T x T tiles, every tile runs through
+ * the same plan, and the tiles' outputs are blended back into one image without seams.  Nothing in the reference: it pads whole images.
+ * The image is what SSDN_OP_IMAGE_IN reads: upright uint8 img[y][x][c] of h x w x C, tight pitch w C, C = 1 or 3, on the device.  Tiles keep
+ * the package's swapped axes: tensor axis 2 runs along the image's x, axis 3 along its y.  tests/tile_ref.py is this text in numpy.
+ * The tiling.  T: the tile edge, a positive multiple of 32 (NoiseNetwork.input_wh_mul()).  O: the overlap, a multiple of 32 with
+ * 0 <= 2 O <= T.  S = T - O.  Per image axis of length n:
+ *     K(n) = 1 if n <= T, otherwise ceil((n - O) / S);   origins o_k = k S, k < K(n)
+ *   Every tile is T x T whatever the image (square: a blind-spot model takes it; one plan shape for a folder of pictures).  Every origin is a
+ *   multiple of 32, so a tile's pooling grid is the whole image's.  The last tile may reach past n: there it sees the reflection r(., n) of
+ *   SSDN_OP_IMAGE_IN (any pad length, r(k, 1) = 0).  S >= T / 2: a position is covered by one or two tiles per axis, never three, and two
+ *   neighbouring tiles overlap by exactly O.  Tiles are numbered k = ky Kx + kx, row-major over the upright image, x fastest;
+ *   Kx = K(w), Ky = K(h).
+ *   The tiles covering position p of an axis:  kb = min(p / S, K - 1), d = p - kb S.
+ *     kb >= 1 and d < O: blended -- a = tile kb - 1 at local d + S, b = tile kb at local d, t = fl32((float)(2 d + 1) / (float)(2 O))
+ *     otherwise:         single  -- tile kb at local d
+ *   Blend, in fp32, every operation rounded on its own (__fsub_rn, __fmul_rn, __fadd_rn, a true division: no contraction reaches it):
+ *     lerp(a, b, t) = a + t (b - a), a the lower-numbered tile; first along x for each of the one or two y-tiles, then along y.
+ *   lerp(a, a, t) = a for finite a, and a position under one tile is that tile's value bit for bit: tiles that agree blend to what they
+ *   agree on.  NaN propagates; q(NaN) = 0 as in SSDN_OP_IMAGE_OUT.
+ * TILE_IN: the tiles k0 .. k0 + B - 1 of the grid into dst [B,C,T,T], (ox, oy) the origin of tile k0 + b; every element is written:
+ *     dst[b,c,i,j] = (float)src[(r(oy + j, h) w + r(ox + i, w)) C + c] / 255.f          (for a single tile: SSDN_OP_IMAGE_IN's value)
+ * TILE_OUT: store is fp32 [Kx Ky, C, T, T], the network's output for every tile of the image; for every x < w, y < h:
+ *     mode 0: bytes,  dst[(y w + x) C + c] = q(blend)   with SSDN_OP_IMAGE_OUT's q      (the denoised picture)
+ *     mode 1: fp32,   dst[(c h + y) w + x] = blend      upright [C,h,w]                 (the posterior std map: no transposition on the host)
+ *   Gather form: each output element is written once by one thread, no atomics, the same bits on every launch; nothing outside the
+ *   w h C elements of dst is written.
+ * Kernels (csrc/tile_io.hip): k_tile_in, one workgroup per (32 x 64 patch of tensor axes 2 x 3 of a tile, tile);
+ * k_tile_out, one workgroup per (32 x 64 patch of the image's x x y): store reads run along tensor axis 3, image accesses along x, the
+ * transposition goes through an LDS tile of odd pitch; offsets are 64-bit; the grid of tiles is arithmetic, there are no device tables.
+ * Argument errors are raised before any device call (text prefixed "tile_in:" / "tile_out:"): a NULL pointer, C not 1 or 3, w or h < 1 or
+ * above 2^30, T not a positive multiple of 32, O negative, not a multiple of 32 or 2 O > T, Kx or Ky differing from K(w), K(h),
+ * w h C >= 2^31, B < 1 or a tile range outside the grid, src_bytes (dst_bytes) below what the image needs, a mode other than 0 or 1, grid
+ * limits (B or T / 32 above 65535; ceil(w / 32) above 65535).  Adding these ops changed no existing struct: the ABI version stays. */
+typedef struct ssdn_tile_in_args {
+    const uint8_t* src;   /* the image, device */
+    int64_t src_bytes;    /* >= w h C */
+    int32_t w, h, C;
+    int32_t T, O, Kx, Ky;
+    int32_t k0, B;        /* the tiles k0 .. k0 + B - 1 */
+    float* dst;           /* out [B,C,T,T]: every element is written */
+} ssdn_tile_in_args;
+
+typedef struct ssdn_tile_out_args {
+    const float* store;   /* [Kx Ky, C, T, T] */
+    int32_t w, h, C;
+    int32_t T, O, Kx, Ky;
+    int32_t mode;         /* 0: uint8 [h][w][C]; 1: fp32 [C][h][w] */
+    void* dst;            /* out, device */
+    int64_t dst_bytes;    /* >= w h C (mode 0), 4 w h C (mode 1) */
+} ssdn_tile_out_args;
 
 /* ---- SSDN_OP_INPUT_GRAD --------------------------------------------------------------------
  * replaces: the data gradient autograd propagates into the network input through the first conv (noise_network.py:69-71) and the

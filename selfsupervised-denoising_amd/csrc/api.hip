@@ -115,6 +115,8 @@ int ssdn_struct_size(int op_type) {
         case SSDN_OP_IMAGE_IN: return (int)sizeof(ssdn_image_in_args);
         case SSDN_OP_IMAGE_OUT: return (int)sizeof(ssdn_image_out_args);
         case SSDN_OP_NOISE_EST: return (int)sizeof(ssdn_noise_est_args);
+        case SSDN_OP_TILE_IN: return (int)sizeof(ssdn_tile_in_args);
+        case SSDN_OP_TILE_OUT: return (int)sizeof(ssdn_tile_out_args);
         default: return -1;
     }
 }
@@ -417,6 +419,8 @@ int ssdn_run_ops(const ssdn_op* ops, int n, void* stream) {
             case SSDN_OP_IMAGE_IN: rc = launch_image_in((const ssdn_image_in_args*)p, s); break;
             case SSDN_OP_IMAGE_OUT: rc = launch_image_out((const ssdn_image_out_args*)p, s); break;
             case SSDN_OP_NOISE_EST: rc = launch_noise_est((const ssdn_noise_est_args*)p, s); break;
+            case SSDN_OP_TILE_IN: rc = launch_tile_in((const ssdn_tile_in_args*)p, s); break;
+            case SSDN_OP_TILE_OUT: rc = launch_tile_out((const ssdn_tile_out_args*)p, s); break;
             case SSDN_OP_ZERO: {
                 const ssdn_zero_args* z = (const ssdn_zero_args*)p;
                 if (z->bytes & 15) return ssdn_set_error("op %d: zero size must be a multiple of 16", i);

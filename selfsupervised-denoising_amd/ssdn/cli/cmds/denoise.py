@@ -1,8 +1,10 @@
-"""`ssdn denoise --model M --input I --output O [--noise_param P|auto] [--batch_size B] [--bucket N] [--uniform] [--std] [--recursive]`:
+"""`ssdn denoise --model M --input I --output O [--noise_param P|auto] [--batch_size B] [--bucket N] [--uniform] [--std] [--recursive]
+[--tile T] [--overlap O]`:
 denoise already noisy images with a trained model (the reference has no such command: its evaluator takes clean datasets and adds
 the noise itself).  I: an image file or a folder of images (file discovery and channel conversion of datasets/folder.py); writes
 O/<relative stem>.png, with --std O/<relative stem>_std.npy (float32 [C,h,w] posterior std dev, ssdn models only), and O/denoise.csv
-with one row per image (with --noise_param auto also the noise parameter estimated for it).  PNG decode and encode stay on the host
+with one row per image (with --noise_param auto also the noise parameter estimated for it, with --tile also the number of tiles it was
+cut into).  PNG decode and encode stay on the host
 with PIL; everything between is `Denoiser.denoise`."""
 import os
 from typing import Dict, List, Tuple
@@ -44,6 +46,11 @@ class DenoiseCommand(Command):
         p.add_argument("--std", action="store_true",
                        help="Also write <stem>_std.npy: the per-pixel posterior std dev, float32 [C,h,w] (ssdn models only).")
         p.add_argument("--recursive", action="store_true", help="Also take the images of the folder's sub-folders.")
+        p.add_argument("--tile", type=int, default=None,
+                       help="Denoise every image wider or taller than this (a multiple of 32) in overlapping tiles of this edge through one "
+                            "plan: images of any size in bounded memory; denoise.csv then gains a tiles column.")
+        p.add_argument("--overlap", type=int, default=None,
+                       help="The overlap of neighbouring tiles (a multiple of 32, at most half of --tile; default a quarter of it).")
 
     def execute(self, args: Dict):
         import numpy as np
@@ -56,7 +63,7 @@ class DenoiseCommand(Command):
         denoiser = Denoiser.from_state_dict(sd["denoiser"] if "denoiser" in sd else sd)
         channels = denoiser.cfg[ConfigValue.IMAGE_CHANNELS]
         opts = dict(noise_param=args.get("noise_param"), batch_size=args.get("batch_size") or 1, bucket=args.get("bucket"),
-                    uniform=bool(args.get("uniform")), std=bool(args.get("std")))
+                    uniform=bool(args.get("uniform")), std=bool(args.get("std")), tile=args.get("tile"), overlap=args.get("overlap"))
         denoiser.denoise([], **opts)                    # (the model's refusals, before a file is opened or a directory made)
         base, files = find_images(args["input"], bool(args.get("recursive")))
         images = []
@@ -70,7 +77,7 @@ class DenoiseCommand(Command):
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "denoise.csv"), "w") as csv:
             csv.write(",".join(["file", "width", "height"] + (["noise_std"] if "noise_std" in res else [])
-                               + (["noise_param"] if "noise_param" in res else [])) + "\n")
+                               + (["noise_param"] if "noise_param" in res else []) + (["tiles"] if "tiles" in res else [])) + "\n")
             for k, path in enumerate(files):
                 stem = os.path.splitext(os.path.relpath(path, base))[0]
                 os.makedirs(os.path.dirname(os.path.join(out_dir, stem)) or out_dir, exist_ok=True)
@@ -80,5 +87,6 @@ class DenoiseCommand(Command):
                 h, w = images[k].shape[:2]
                 csv.write(",".join([os.path.relpath(path, base), str(w), str(h)]
                                    + (["{:.6f}".format(res["noise_std"][k])] if "noise_std" in res else [])
-                                   + (["{:.9g}".format(res["noise_param"][k])] if "noise_param" in res else [])) + "\n")
+                                   + (["{:.9g}".format(res["noise_param"][k])] if "noise_param" in res else [])
+                                   + ([str(res["tiles"][k])] if "tiles" in res else [])) + "\n")
         return res

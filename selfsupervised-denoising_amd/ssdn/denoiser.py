@@ -459,12 +459,34 @@ class Denoiser(nn.Module):
             raise ValueError("denoise: batch_size must be at least 1")
         return bucket, batch_size
 
-    def _denoise_groups(self, imgs: List[Tensor], bucket: int, uniform: bool) -> Dict[Tuple[int, int], List[int]]:
-        """the images' indices by padded shape on tensor axes 2 and 3 = along the image's x and y (NoisyDataset.get_output_size: uniform,
-        multiple, square)"""
-        big = (max(t.shape[1] for t in imgs), max(t.shape[0] for t in imgs))
+    @staticmethod
+    def _tile_options(tile: Optional[int], overlap: Optional[int]) -> Tuple[Optional[int], Optional[int]]:
+        """`denoise`'s tile and overlap as the (T, O) of SSDN_OP_TILE_IN, or (None, None) without tiling (ValueError otherwise)"""
+        mul = NoiseNetwork.input_wh_mul()
+        if tile is None:
+            if overlap is not None:
+                raise ValueError("denoise: overlap needs tile")
+            return None, None
+        tile = int(tile)
+        if tile < mul or tile % mul:
+            raise ValueError("denoise: tile must be a positive multiple of %d, got %d" % (mul, tile))
+        if overlap is None:
+            overlap = min(max(mul, tile // 4 // mul * mul), tile // 2 // mul * mul)
+        overlap = int(overlap)
+        if overlap < 0 or overlap % mul:
+            raise ValueError("denoise: overlap must be a multiple of %d and not negative, got %d" % (mul, overlap))
+        if 2 * overlap > tile:
+            raise ValueError("denoise: 2 * overlap must not exceed tile, got overlap %d for tile %d" % (overlap, tile))
+        return tile, overlap
+
+    def _denoise_groups(self, imgs: List[Tensor], bucket: int, uniform: bool, members: Optional[List[int]] = None) -> Dict[Tuple[int, int], List[int]]:
+        """the images' indices (all, or `members`) by padded shape on tensor axes 2 and 3 = along the image's x and y
+        (NoisyDataset.get_output_size: uniform, multiple, square)"""
+        members = list(range(len(imgs))) if members is None else members
+        big = (max(imgs[k].shape[1] for k in members), max(imgs[k].shape[0] for k in members))
         groups: Dict[Tuple[int, int], List[int]] = {}
-        for k, t in enumerate(imgs):
+        for k in members:
+            t = imgs[k]
             H, W = ((n + bucket - 1) // bucket * bucket for n in (big if uniform else (t.shape[1], t.shape[0])))
             if self.cfg[ConfigValue.BLINDSPOT]:
                 H = W = max(H, W)
@@ -510,8 +532,91 @@ class Denoiser(nn.Module):
         return {"sigma": float(row[0]), "lambda": float(row[1]), "n": int(row[2]), "classes_used": int(row[3]),
                 "nlf_sigma": row[4:12].clone(), "nlf_mean": row[12:20].clone(), "noise_param": param}
 
+    def _tile_buffer(self, name: str, numel: int, dtype, pinned: bool = False) -> Tensor:
+        """a buffer of `_denoise_tiled`, owned by the Denoiser (no engine has the image's shape), allocated on first use and grown on demand"""
+        buf = self.__dict__.setdefault("_tile", {})
+        if name not in buf or buf[name].numel() < numel:
+            buf[name] = (torch.zeros((numel,), dtype=dtype).pin_memory() if pinned else torch.zeros((numel,), dtype=dtype, device=self.device))
+        return buf[name]
+
+    _TILE_HEAD = 16             # the byte buffer of a tiled image starts with SSDN_OP_NOISE_EST's tables: offs int64 [1], ext int32 [2]
+
+    def _denoise_tiled(self, t: Tensor, T: int, O: int, value, kind: Optional[str], batch_size: int, std: bool) -> Dict:
+        """One image larger than the tile, through the inference plan (B, T, T) in overlapping tiles (include/ssdn_hip.h, SSDN_OP_TILE_IN /
+        SSDN_OP_TILE_OUT).  t: uint8 CPU tensor [h, w, C]; value: the noise parameter, None, or "auto" with `kind`
+        the estimator's.  One pinned upload; per batch of at most `batch_size` tiles TILE_IN into the engine's input, the run, a device
+        copy of its output into the tile store (with std also the posterior launch and a copy into a second store); then TILE_OUT, one
+        download and one synchronisation.  A store is Kx Ky C T^2 4 bytes.  -> {"out", "tiles", ["noise_std"], ["std"], ["noise_param"]}."""
+        from ssdn.hip import lib as L
+        from ssdn.hip import engine as E
+        ssdn_pipe = self._pipeline == Pipeline.SSDN
+        h, w, Cn = (int(v) for v in t.shape)
+        Kx, Ky = L.tile_count(w, T, O), L.tile_count(h, T, O)
+        n, nb, head, S = Kx * Ky, w * h * Cn, self._TILE_HEAD, T - O
+        if nb >= 2 ** 31:
+            raise ValueError("denoise: an image of %d x %d x %d is beyond the 2^31 bytes the tile ops address" % (w, h, Cn))
+        host = self._tile_buffer("host_in", head + nb, torch.uint8, pinned=True)
+        dev = self._tile_buffer("dev_in", head + nb, torch.uint8)
+        host[:8].view(torch.int64)[0] = 0
+        host[8:16].view(torch.int32).copy_(torch.tensor([w, h], dtype=torch.int32))
+        host[head:head + nb] = t.reshape(-1)
+        dev[:head + nb].copy_(host[:head + nb], non_blocking=True)
+        img = dev[head:head + nb]
+        auto = isinstance(value, str)
+        if auto:
+            # one estimate over the whole image (B = 1, a tensor of the image's own extent): Denoiser.estimate_noise's, whatever the tiling
+            hist = self._tile_buffer("est_hist", L.NOISE_EST_CLASSES * L.NOISE_EST_BINS, torch.int32)
+            ssum = self._tile_buffer("est_ssum", L.NOISE_EST_CLASSES, torch.int64)
+            est = self._tile_buffer("est", L.NOISE_EST_NEST, torch.float64)
+            par = self._tile_buffer("est_param", 1, torch.float32)
+            a = L.NoiseEstArgs(E._ptr(img), nb, E._ptr(dev), E._ptr(dev, 8), 1, Cn, w, h, L.NOISE_EST_KIND[kind], E._ptr(hist), E._ptr(ssum),
+                               E._ptr(est), E._ptr(par))
+            E.OpList([("noise_est", a)]).run(E.current_stream())
+        store = self._tile_buffer("store", n * Cn * T * T, torch.float32)[:n * Cn * T * T].view(n, Cn, T, T)
+        store_std = self._tile_buffer("store_std", n * Cn * T * T, torch.float32)[:n * Cn * T * T].view(n, Cn, T, T) if std else None
+        nstd = []                                            # per tile: a 0-dim device tensor
+        for k0 in range(0, n, batch_size):
+            B = min(batch_size, n - k0)
+            eng = self._engine(B, T, T, False)
+            data = [E.tile_in(img, w, h, T, O, k0, eng.inp)]
+            if auto:                                         # broadcast on the device: no host round trip
+                eng.noise_param.copy_(par[:1].expand(B))
+                data += [torch.zeros(0), {NoisyDataset.Metadata.INPUT_NOISE_VALUES: eng.noise_param}]
+            elif value is not None:
+                data += [torch.zeros(0), {NoisyDataset.Metadata.INPUT_NOISE_VALUES: torch.full((B, 1, 1, 1), value)}]
+            self._run(data, clone=False)                     # (no_grad: the inference plan, whose input is already in place)
+            store[k0:k0 + B].copy_(eng.pme if ssdn_pipe else eng.main.tensor("out32"))
+            if std:
+                store_std[k0:k0 + B].copy_(eng.posterior(cov=False, std=True)["std"])
+            if ssdn_pipe:
+                for b in range(B):
+                    if eng.style == "poisson":               # a map: over the part of the tile inside the image
+                        ky, kx = divmod(k0 + b, Kx)
+                        nstd.append(eng.noise_std[b, :min(T, w - kx * S), :min(T, h - ky * S)].mean())
+                    else:
+                        nstd.append(eng.noise_std[0 if self._const else b].clone())
+        res: Dict = {"tiles": n}
+        dev_out = self._tile_buffer("dev_out", nb, torch.uint8)
+        host_out = self._tile_buffer("host_out", nb, torch.uint8, pinned=True)
+        E.tile_out(store, w, h, T, O, 0, dev_out)
+        host_out[:nb].copy_(dev_out[:nb], non_blocking=True)
+        if std:
+            dev_std = self._tile_buffer("dev_std", nb, torch.float32)
+            host_std = self._tile_buffer("host_std", nb, torch.float32, pinned=True)
+            E.tile_out(store_std, w, h, T, O, 1, dev_std)
+            host_std[:nb].copy_(dev_std[:nb], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        res["out"] = host_out[:nb].view(h, w, Cn).clone()
+        if std:
+            res["std"] = host_std[:nb].view(Cn, h, w).clone()
+        if ssdn_pipe:
+            res["noise_std"] = float(torch.stack(nstd).cpu().to(torch.float64).mean())
+        if auto:
+            res["noise_param"] = float(par.cpu()[0])
+        return res
+
     def denoise(self, images: List, noise_param=None, batch_size: int = 1, bucket: Optional[int] = None, uniform: bool = False,
-                std: bool = False) -> Dict:
+                std: bool = False, tile: Optional[int] = None, overlap: Optional[int] = None) -> Dict:
         """Denoise already noisy images.  images: uint8 arrays or tensors [h, w] or [h, w, C], upright as PIL hands them out, of any and
         differing sizes, C the model's channel count.  Every image is reflection-padded bottom and right to a multiple of `bucket`
         (default and unit: NoiseNetwork.input_wh_mul(); larger values trade padding for fewer distinct plans -- at most _MAX_ENGINES are
@@ -527,9 +632,23 @@ class Denoiser(nn.Module):
         image; an image too small or too saturated for an estimate raises ValueError naming its index.
         -> {"out": uint8 CPU tensors of the inputs' shapes, in input order}; ssdn models also "noise_std": per image the mean of
         NOISE_STD_DEV over its extent; std=True (ssdn only) adds "std": float32 [C, h, w] upright posterior std maps (Denoiser.posterior's).
+        tile=T (a positive multiple of 32; overlap=O a multiple of 32 with 0 <= 2 O <= T, default T / 4 rounded down to a multiple of 32, at
+        least 32 and at most T / 2 rounded down to one; overlap without tile and values outside these raise ValueError before any device
+        work): an image with w <= T and h <= T takes the route above untouched, byte for byte (uniform=True then pads to the largest of
+        THESE images); every other image is cut into T x T tiles whose origins are multiples of T - O, which run through ONE inference plan
+        (B, T, T) in batches of at most batch_size tiles of that image and are blended linearly across the overlaps (SSDN_OP_TILE_IN /
+        SSDN_OP_TILE_OUT, csrc/tile_io.hip, include/ssdn_hip.h for the definition); bucket and uniform do not apply
+        to it.  Its bytes go up once into a buffer the Denoiser owns and come down once; between them the tiles' outputs wait in a store of
+        Kx Ky C T^2 4 bytes on the device (~1 GB for 45 megapixels at T = 512, O = 128; std=True keeps a second one), allocated on first
+        use and grown to the largest image.  "auto" estimates ONE parameter over the whole image -- `estimate_noise([image])`'s, bit for
+        bit, whatever the tiling -- and every tile takes it.  "noise_std" of a tiled image is the float64 mean over its tiles of the
+        per-tile value (poisson: of each tile's map over the part of the tile inside the image); a model that estimates the noise level
+        from its input (a variable unknown noise level: the sigma network) does so per TILE, a known difference from a whole-image run.
+        With tile the result gains "tiles": Kx Ky per image, 1 for an image that was not tiled.
         Like `posterior` it never becomes the forward that backward() / optimizer_step() / accumulate_metrics() act on."""
         ssdn_pipe = self._pipeline == Pipeline.SSDN
         value = self._noise_param_value(noise_param)
+        tile, overlap = self._tile_options(tile, overlap)
         if std and not ssdn_pipe:
             raise ValueError("denoise: std=True needs a posterior: the %s pipeline has none (ssdn models only)" % self._pipeline.value)
         bucket, batch_size = self._denoise_options(bucket, batch_size)
@@ -544,12 +663,24 @@ class Denoiser(nn.Module):
             res["noise_std"] = [None] * len(imgs)
         if std:
             res["std"] = [None] * len(imgs)
+        if tile is not None:
+            res["tiles"] = [1] * len(imgs)
         if not imgs:
             return res
-        groups = self._denoise_groups(imgs, bucket, uniform)
+        tiled = [k for k, t in enumerate(imgs) if tile is not None and (t.shape[1] > tile or t.shape[0] > tile)]
+        whole = [k for k in range(len(imgs)) if k not in tiled]
+        groups = self._denoise_groups(imgs, bucket, uniform, whole) if whole else {}
         keep = (self._last_engine, getattr(self, "_has_loss_last", None))
         try:
             with torch.no_grad():
+                for k in tiled:
+                    one = self._denoise_tiled(imgs[k], tile, overlap, value, kind if auto else None, batch_size, std)
+                    if auto and not math.isfinite(one["noise_param"]):
+                        raise ValueError("denoise: image %d has too few valid 3x3 windows for a noise estimate (it is smaller "
+                                         "than 3x3 or saturated): pass noise_param as a number" % k)
+                    one["out"] = one["out"] if images[k].ndim == 3 else one["out"][:, :, 0]
+                    for name, v in one.items():
+                        res[name][k] = v
                 for (H, W), members in groups.items():
                     for lo in range(0, len(members), batch_size):
                         idx = members[lo:lo + batch_size]

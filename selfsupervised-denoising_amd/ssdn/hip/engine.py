@@ -43,6 +43,41 @@ def current_stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
+def _tile_check(name: str, t: torch.Tensor, dtype, numel: int):
+    if t.dtype != dtype or not t.is_contiguous() or t.device.type != "cuda" or t.numel() < numel:
+        raise L.SsdnHipError("%s must be a contiguous %s device tensor of at least %d elements" % (name, dtype, numel))
+
+
+def tile_in(img: torch.Tensor, w: int, h: int, T: int, O: int, k0: int, dst: torch.Tensor) -> torch.Tensor:
+    """The tiles k0 .. k0 + B - 1 of one image into dst [B,C,T,T] (SSDN_OP_TILE_IN, csrc/tile_io.hip; the tiling is defined in
+    include/ssdn_hip.h): one launch on torch's current stream that divides by 255, transposes to the package's swapped axes and reflects
+    where a tile reaches past the image.  img: the image's bytes on the device, uint8 [h w C] upright and interleaved; dst: normally an
+    inference engine's `inp`, which `Denoiser._run` then takes without a copy.  Belongs to no engine: the image is not of a plan's shape."""
+    B, Cn = int(dst.shape[0]), int(dst.shape[1])
+    _tile_check("tile_in: img", img, torch.uint8, w * h * Cn)
+    _tile_check("tile_in: dst", dst, torch.float32, B * Cn * T * T)
+    if tuple(dst.shape) != (B, Cn, T, T):
+        raise L.SsdnHipError("tile_in: dst must be [B, C, %d, %d]" % (T, T))
+    a = L.TileInArgs(_ptr(img), img.numel(), w, h, Cn, T, O, L.tile_count(w, T, O), L.tile_count(h, T, O), k0, B, _ptr(dst))
+    OpList([("tile_in", a)]).run(current_stream())
+    return dst
+
+
+def tile_out(store: torch.Tensor, w: int, h: int, T: int, O: int, mode: int, dst: torch.Tensor) -> torch.Tensor:
+    """The tiles' values of one image blended back into that image (SSDN_OP_TILE_OUT): one launch on torch's current stream.  store:
+    fp32 [Kx Ky, C, T, T] on the device; mode 0: dst uint8, the picture's bytes [h, w, C] (clipped, * 255, truncated); mode 1: dst fp32,
+    upright planes [C, h, w].  Only the first w h C elements of dst are written.  Does not synchronise."""
+    Kx, Ky = L.tile_count(w, T, O), L.tile_count(h, T, O)
+    Cn = int(store.shape[1])
+    if tuple(store.shape) != (Kx * Ky, Cn, T, T):
+        raise L.SsdnHipError("tile_out: store must be [%d, C, %d, %d]" % (Kx * Ky, T, T))
+    _tile_check("tile_out: store", store, torch.float32, Kx * Ky * Cn * T * T)
+    _tile_check("tile_out: dst", dst, torch.float32 if mode else torch.uint8, w * h * Cn)
+    a = L.TileOutArgs(_ptr(store), w, h, Cn, T, O, Kx, Ky, mode, _ptr(dst), dst.numel() * dst.element_size())
+    OpList([("tile_out", a)]).run(current_stream())
+    return dst
+
+
 class DeviceNet:
     """One NoiseNetwork instance on the device for a fixed input shape: buffers + materialised fwd/bwd/pack op lists."""
 

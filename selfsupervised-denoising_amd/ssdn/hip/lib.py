@@ -17,7 +17,8 @@ MAX_TAPS = 9
 OP = dict(pack_input=1, conv=2, pool_fwd=3, pool_bwd=4, upsum_bwd=5, unrot_fwd=6, unrot_bwd=7, wgrad=8, wreduce=9,
           wpack=10, grad_pack=11, head_ssdn=12, head_final=13, spatial_mean=14, mse=15, mask_mse=16, adam=17,
           metrics=18, zero=19, event_record=20, noise=21, input_grad=22, head_vjp=23,
-          mse_vjp=24, accum=25, head_posterior=26, ssim=27, calibration=28, image_in=29, image_out=30, noise_est=31)
+          mse_vjp=24, accum=25, head_posterior=26, ssim=27, calibration=28, image_in=29, image_out=30, noise_est=31,
+          tile_in=32, tile_out=33)
 
 i32, f32, vp = C.c_int32, C.c_float, C.c_void_p
 
@@ -197,13 +198,28 @@ NOISE_EST_CLASSES, NOISE_EST_BINS, NOISE_EST_NEST = 8, 1024, 20        # SSDN_NO
 NOISE_EST_KIND = dict(gauss=0, poisson=1)
 
 
+class TileInArgs(C.Structure):
+    _fields_ = [("src", vp), ("src_bytes", C.c_int64), ("w", i32), ("h", i32), ("C", i32), ("T", i32), ("O", i32), ("Kx", i32), ("Ky", i32),
+                ("k0", i32), ("B", i32), ("dst", vp)]
+
+
+class TileOutArgs(C.Structure):
+    _fields_ = [("store", vp), ("w", i32), ("h", i32), ("C", i32), ("T", i32), ("O", i32), ("Kx", i32), ("Ky", i32), ("mode", i32),
+                ("dst", vp), ("dst_bytes", C.c_int64)]
+
+
+def tile_count(n: int, T: int, O: int) -> int:
+    """K(n) of include/ssdn_hip.h (SSDN_OP_TILE_IN): the T-sized tiles of overlap O along an image axis of n elements"""
+    return 1 if n <= T else -(-(n - O) // (T - O))
+
+
 ARG_TYPES = dict(pack_input=PackInputArgs, conv=ConvArgs, pool_fwd=PoolArgs, pool_bwd=PoolArgs, upsum_bwd=UpsumArgs,
                  unrot_fwd=UnrotArgs, unrot_bwd=UnrotArgs, wgrad=WgradArgs, wreduce=WreduceArgs, wpack=WpackArgs,
                  grad_pack=GradPackArgs, head_ssdn=HeadArgs, head_final=HeadFinalArgs, spatial_mean=SpatialMeanArgs,
                  mse=MseArgs, mask_mse=MseArgs, adam=AdamArgs, metrics=MetricsArgs, zero=ZeroArgs, event_record=EventArgs, noise=NoiseArgs,
                  input_grad=InputGradArgs, head_vjp=HeadVjpArgs, mse_vjp=MseVjpArgs, accum=AccumArgs,
                  head_posterior=HeadPosteriorArgs, ssim=SsimArgs, calibration=CalibrationArgs, image_in=ImageInArgs, image_out=ImageOutArgs,
-                 noise_est=NoiseEstArgs)
+                 noise_est=NoiseEstArgs, tile_in=TileInArgs, tile_out=TileOutArgs)
 
 # every symbol include/ssdn_hip.h declares
 ABI_VERSION = 19      # SSDN_ABI_VERSION of include/ssdn_hip.h this binding mirrors

@@ -9,7 +9,13 @@ images of 512 x 512 and of 768 x 768, one image per batch: per image, between de
 Prints one JSON line.  --trace DIR: runs itself once under `rocprofv3 --kernel-trace --stats` (a child process, nothing else traced) and
 prints the times of k_image_in / k_image_out per size with their algorithmic HBM bytes (in: 1 byte read and 4 written per padded element;
 out: 4 read and 1 written per element of the extent; with --auto also k_noise_est: 1 byte read per element, and k_noise_est_final: the
-32 KiB table) and the share of `--hbm-gbs` they achieve; --csv FILE also writes that table."""
+32 KiB table) and the share of `--hbm-gbs` they achieve; --csv FILE also writes that table.
+--tile measures tiled denoising instead, same model: cost -- a 1024 x 768 image untiled and with tile = 256 and 512
+at the default overlap, at batch sizes 1 and 4, ms per image between device events next to the tile count and the compute overhead
+Kx Ky T^2 / (w h) the overlap implies; big -- one 4096 x 3072 image, tiled only (tile 512), with its time and the peak device memory;
+fidelity -- a 768 x 768 noisy synthetic picture, tile 256 with overlap 0, 32, 64 and 128 against the untiled output: PSNR in dB over the
+bytes and the largest byte difference (random weights: how fast a tile border's influence decays, nothing about a trained model).  With
+--trace DIR it runs itself once under rocprofv3 and prints the times of k_tile_in / k_tile_out per kernel and grid."""
 import argparse
 import csv
 import glob
@@ -101,6 +107,100 @@ def run(args):
     print(json.dumps(res))
 
 
+def run_tile(args):
+    import numpy as np
+    import torch
+    import ssdn
+    from ssdn.denoiser import Denoiser
+    from ssdn.hip import lib as L
+    from ssdn.params import ConfigValue, NoiseAlgorithm, NoiseValue
+    cfg = ssdn.cfg.base()
+    cfg[ConfigValue.ALGORITHM] = NoiseAlgorithm.SELFSUPERVISED_DENOISING
+    cfg[ConfigValue.NOISE_STYLE] = "gauss25"
+    cfg[ConfigValue.NOISE_VALUE] = NoiseValue.KNOWN
+    torch.manual_seed(0)
+    d = Denoiser(ssdn.cfg.infer(cfg, model_only=True), device="cuda:0")
+    d.eval()
+    g = np.random.default_rng(0)
+    res = dict(images=args.images)
+
+    def timed(fn, n):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return round(e0.elapsed_time(e1) / n, 3)
+
+    def picture(h, w):
+        """something smooth with edges plus gaussian noise of sigma 25, as bytes"""
+        yy, xx = np.mgrid[0:h, 0:w]
+        clean = 128 + 70 * np.sin(xx / 37.0) * np.cos(yy / 23.0) + 40 * ((xx // 96 + yy // 64) % 2)
+        return np.clip(clean[:, :, None] + g.normal(0, 25, (h, w, 3)), 0, 255).astype(np.uint8)
+
+    # cost
+    w, h = 1024, 768
+    img = [picture(h, w)]
+    d.denoise(img, noise_param=25)
+    res["untiled_1024x768_ms"] = timed(lambda: d.denoise(img, noise_param=25), args.images)
+    for T in (256, 512):
+        O = Denoiser._tile_options(T, None)[1]
+        n = L.tile_count(w, T, O) * L.tile_count(h, T, O)
+        for bs in (1, 4):
+            fn = lambda: d.denoise(img, noise_param=25, tile=T, batch_size=bs)      # noqa: E731
+            fn()
+            res["tile%d_o%d_b%d_1024x768" % (T, O, bs)] = dict(ms=timed(fn, args.images), tiles=n, overhead=round(n * T * T / (w * h), 3))
+    d._engines.clear()
+    # fidelity
+    pic = [picture(768, 768)]
+    ref = d.denoise(pic, noise_param=25)["out"][0].numpy().astype(np.float64)
+    for O in (0, 32, 64, 128):
+        out = d.denoise(pic, noise_param=25, tile=256, overlap=O, batch_size=4)["out"][0].numpy().astype(np.float64)
+        mse = float(((out - ref) ** 2).mean())
+        res["fidelity_768_t256_o%d" % O] = dict(psnr_db=round(10 * np.log10(255.0 ** 2 / mse), 2) if mse > 0 else None,
+                                                max_byte_diff=int(np.abs(out - ref).max()), differing=round(float((out != ref).mean()), 4))
+    d._engines.clear()
+    torch.cuda.empty_cache()
+    # big: beyond the untiled route's tested range, tiled only
+    w, h, T = 4096, 3072, 512
+    O = Denoiser._tile_options(T, None)[1]
+    big = [picture(h, w)]
+    torch.cuda.reset_peak_memory_stats()
+    fn = lambda: d.denoise(big, noise_param=25, tile=T, batch_size=4)      # noqa: E731
+    fn()
+    res["tile%d_o%d_b4_4096x3072" % (T, O)] = dict(ms=timed(fn, 3), tiles=L.tile_count(w, T, O) * L.tile_count(h, T, O),
+                                                  peak_device_MB=round(torch.cuda.max_memory_allocated() / 2 ** 20, 1))
+    print(json.dumps(res))
+
+
+def trace_tile(args):
+    os.makedirs(args.trace, exist_ok=True)
+    cmd = ["timeout", "-k", "10", "400", "rocprofv3", "--kernel-trace", "--stats", "-d", args.trace, "-o", "tile", "--output-format", "csv",
+           "--", sys.executable, os.path.abspath(__file__), "--tile", "--images", str(args.images)]
+    r = subprocess.run(cmd)
+    if r.returncode != 0:
+        sys.exit("rocprofv3 run failed with exit status %d" % r.returncode)
+    traces = sorted(glob.glob(os.path.join(args.trace, "**", "*kernel_trace.csv"), recursive=True), key=os.path.getmtime)
+    if not traces:
+        sys.exit("no kernel_trace.csv under " + args.trace)
+    groups = {}
+    with open(traces[-1]) as fh:
+        for row in csv.DictReader(fh):
+            name = row["Kernel_Name"]
+            name = name[5:] if name.startswith("void ") else name
+            if name.startswith("k_tile_"):
+                grid = "x".join(str(row.get(k, "?")) for k in ("Grid_Size_X", "Grid_Size_Y", "Grid_Size_Z"))
+                groups.setdefault((name.split("(")[0], grid), []).append(int(row["End_Timestamp"]) - int(row["Start_Timestamp"]))
+    out = {}
+    for (name, grid), dur in sorted(groups.items()):
+        dur = dur[1:] if len(dur) > 1 else dur                     # (the first launch of a kind loads the code object / a cold cache)
+        out["%s grid %s" % (name, grid)] = dict(calls=len(dur), avg_us=round(sum(dur) / len(dur) / 1e3, 2), min_us=round(min(dur) / 1e3, 2),
+                                               max_us=round(max(dur) / 1e3, 2))
+    print(json.dumps(dict(kernel_times=out, source=os.path.basename(traces[-1]))))
+
+
 def trace(args):
     os.makedirs(args.trace, exist_ok=True)
     cmd = ["timeout", "-k", "10", "400", "rocprofv3", "--kernel-trace", "--stats", "-d", args.trace, "-o", "denoise", "--output-format", "csv",
@@ -153,8 +253,11 @@ def main():
     ap.add_argument("--auto", action="store_true", help="also time Denoiser.denoise(noise_param='auto'), alternating with the number")
     ap.add_argument("--trace", metavar="DIR", default=None, help="run once under rocprofv3 --kernel-trace --stats and summarise")
     ap.add_argument("--csv", metavar="FILE", default=None, help="with --trace: also write the per-kernel table there")
+    ap.add_argument("--tile", action="store_true", help="measure tiled denoising instead: cost, one large image, fidelity against the untiled output")
     args = ap.parse_args()
-    if args.trace:
+    if args.tile:
+        (trace_tile if args.trace else run_tile)(args)
+    elif args.trace:
         trace(args)
     else:
         run(args)
