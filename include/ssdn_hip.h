@@ -79,7 +79,8 @@ enum ssdn_op_type {
     SSDN_OP_IMAGE_OUT = 30,     /* an fp32 batch -> uint8 images of differing sizes: cropped to each extent, clipped, * 255, truncated, transposed (no planned list holds it) */
     SSDN_OP_NOISE_EST = 31,     /* a blind per-image noise-level estimate (gauss sigma, poisson lambda) from the packed uint8 images SSDN_OP_IMAGE_IN reads (no planned list holds it) */
     SSDN_OP_TILE_IN = 32,       /* one uint8 image of any size -> a batch of its fixed-size overlapping tiles: / 255, transposed, reflected beyond the image (no planned list holds it) */
-    SSDN_OP_TILE_OUT = 33       /* the fp32 tiles of one image -> that image, blended across the overlaps: bytes or upright fp32 planes (no planned list holds it) */
+    SSDN_OP_TILE_OUT = 33,      /* the fp32 tiles of one image -> that image, blended across the overlaps: bytes or upright fp32 planes (no planned list holds it) */
+    SSDN_OP_POOL_PATCH = 34     /* a minibatch of training patches cut out of a device-resident pool of uint8 images: crop, dihedral transform, / 255 (+ Noise2Void) (no planned list holds it) */
 };
 
 /* One record of the op list.  `args` points at the matching ssdn_*_args struct (host memory).
@@ -809,6 +810,47 @@ typedef struct ssdn_tile_out_args {
     void* dst;            /* out, device */
     int64_t dst_bytes;    /* >= w h C (mode 0), 4 w h C (mode 1) */
 } ssdn_tile_out_args;
+
+/* ---- SSDN_OP_POOL_PATCH -------------------------------------------------------------------------
+ * Training on images that are ALREADY noisy: every training image is decoded once, its bytes stay on the device, and one launch cuts a whole
+ * minibatch of P x P patches out of that pool.  Nothing is synthesised: the op is a gather.  tests/patch_pool_ref.py is this text in numpy.
+ * The pool.  N images back to back, no alignment padding; image i is planar uint8 [C, rows_i, cols_i] at byte offsets[i], sizes[i] =
+ *   (rows_i, cols_i) -- the layout of the dataset's own tensor, whatever it calls H and W.  params[i] (may be NULL): its noise parameter.
+ * Sample b takes image i = index[b] (chosen on the host: the sampling order and its checkpoints stay what they are; the host checks
+ *   0 <= index[b] < N before upload) and ONE Philox4x32-10 block (csrc/philox.h), counter (b, 5, offset lo, offset hi), key (seed lo,
+ *   seed hi) -- stream 5 (NS_CROP) is this op's -> words v0 .. v3.  All integer arithmetic:
+ *     span_x = max(cols - P, 0) + 1,  x0 = umulhi(v0, span_x);   span_y = max(rows - P, 0) + 1,  y0 = umulhi(v1, span_y)
+ *     d = augment ? v2 >> 29 : 0                                 (one of the eight transforms of the square)
+ * Output element (px, py) (px along tensor axis 3, py along axis 2): (u, v) = (px, py); bit 0 of d swaps u and v; bit 1: u = P - 1 - u;
+ *   bit 2: v = P - 1 - v; the source is column r(x0 + u, cols), row r(y0 + v, rows) with numpy's "reflect" iterated to any length:
+ *     r(t, 1) = 0;  otherwise m = t mod (2 n - 2), r(t, n) = m < n ? m : 2 n - 2 - m
+ *   An image smaller than the patch is extended to the right and downwards only (the host RandomCrop pads both sides: crop positions are
+ *   "distribution only" in this project).  value = (float)byte / 255.f, a true division as SSDN_OP_NOISE's.
+ * Noise2Void (n2v_box > 0): the selection of one pixel per n2v_box x n2v_box box and its neighbour (rx, ry) are SSDN_OP_NOISE's, drawn from
+ *   ITS coordinate stream (3) under the same (seed, offset), in patch coordinates; noisy32 at the selected pixel takes the patch value at
+ *   (rx, ry) in every channel, coords[b, cell] = (c0, c1) as SSDN_OP_NOISE writes them, and ref32 is the unmanipulated patch.
+ * param_out[b C + c] = params[index[b]] for every c (needs params); origin_out[b] = (x0, y0, d).
+ * Kernel (csrc/patch_pool.hip): one thread per output pixel, all channels; byte addresses are 64-bit:
+ *   offsets[i] + (c rows + row) cols + col.  No atomics, no LDS, no state between launches; every element of every given output is written.
+ * Argument errors are raised before any device call (text prefixed "pool_patch:"): a NULL pool, offsets, sizes, index or noisy32; N, B, C or
+ *   P below 1; B C P P >= 2^31; param_out without params; with n2v_box > 0: no coords, P not a multiple of n2v_box, n2v_radius < 1 or P < 2.
+ * Adding this op changed no existing struct: the ABI version stays. */
+typedef struct ssdn_pool_patch_args {
+    const uint8_t* pool;      /* the packed images, device */
+    const int64_t* offsets;   /* [N] byte offset of every image */
+    const int32_t* sizes;     /* [N][2] (rows, cols) */
+    const float* params;      /* [N] per-image noise parameter, may be NULL */
+    const int32_t* index;     /* [B] the image of every sample */
+    float* noisy32;           /* out [B,C,P,P] */
+    float* ref32;             /* out [B,C,P,P], may be NULL: the unmanipulated patch */
+    int64_t* coords;          /* out [B, (P / n2v_box)^2, 2], n2v_box > 0 only */
+    float* param_out;         /* out [B C], may be NULL */
+    int32_t* origin_out;      /* out [B][3] (x0, y0, d), may be NULL */
+    int32_t N, B, C, P;
+    int32_t augment;          /* 0: d = 0 */
+    int32_t n2v_box, n2v_radius;
+    uint64_t seed, offset;
+} ssdn_pool_patch_args;
 
 /* ---- SSDN_OP_INPUT_GRAD --------------------------------------------------------------------
  * replaces: the data gradient autograd propagates into the network input through the first conv (noise_network.py:69-71) and the

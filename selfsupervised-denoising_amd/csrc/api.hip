@@ -117,6 +117,7 @@ int ssdn_struct_size(int op_type) {
         case SSDN_OP_NOISE_EST: return (int)sizeof(ssdn_noise_est_args);
         case SSDN_OP_TILE_IN: return (int)sizeof(ssdn_tile_in_args);
         case SSDN_OP_TILE_OUT: return (int)sizeof(ssdn_tile_out_args);
+        case SSDN_OP_POOL_PATCH: return (int)sizeof(ssdn_pool_patch_args);
         default: return -1;
     }
 }
@@ -421,6 +422,7 @@ int ssdn_run_ops(const ssdn_op* ops, int n, void* stream) {
             case SSDN_OP_NOISE_EST: rc = launch_noise_est((const ssdn_noise_est_args*)p, s); break;
             case SSDN_OP_TILE_IN: rc = launch_tile_in((const ssdn_tile_in_args*)p, s); break;
             case SSDN_OP_TILE_OUT: rc = launch_tile_out((const ssdn_tile_out_args*)p, s); break;
+            case SSDN_OP_POOL_PATCH: rc = launch_pool_patch((const ssdn_pool_patch_args*)p, s); break;
             case SSDN_OP_ZERO: {
                 const ssdn_zero_args* z = (const ssdn_zero_args*)p;
                 if (z->bytes & 15) return ssdn_set_error("op %d: zero size must be a multiple of 16", i);

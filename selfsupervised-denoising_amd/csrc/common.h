@@ -155,6 +155,7 @@ int launch_image_out(const ssdn_image_out_args* a, hipStream_t s);             /
 int launch_noise_est(const ssdn_noise_est_args* a, hipStream_t s);             // noise_est.hip: per-image noise-level estimate from the packed bytes
 int launch_tile_in(const ssdn_tile_in_args* a, hipStream_t s);                 // tile_io.hip: one uint8 image -> a batch of its overlapping fp32 tiles
 int launch_tile_out(const ssdn_tile_out_args* a, hipStream_t s);               // tile_io.hip: the fp32 tiles of one image -> that image, blended
+int launch_pool_patch(const ssdn_pool_patch_args* a, hipStream_t s);           // patch_pool.hip: a minibatch of training patches out of a device-resident image pool
 int launch_mse_vjp(const ssdn_mse_vjp_args* a, hipStream_t s);
 int launch_adam(const ssdn_adam_args* a, hipStream_t s);
 #define ADAM_PACK_MAX 24

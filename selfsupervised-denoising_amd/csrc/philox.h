@@ -1,7 +1,7 @@
 // philox.h -- the library's counter-based random numbers, shared by the training patch stream (elementwise.hip: SSDN_OP_NOISE) and the
 // posterior sampler (head_posterior.hip: SSDN_OP_HEAD_POSTERIOR): Philox4x32-10, the map of 32 random bits to (0, 1] and the Box-Muller
 // normal.  A value is a pure function of (key, counter); the callers lay the counter out as (element, stream, offset lo, offset hi) and key
-// it by the seed.  Streams: 0..4 are SSDN_OP_NOISE's (NS_* in elementwise.hip); PH_STREAM_POSTERIOR and above are the posterior sampler's.
+// it by the seed.  Streams: 0..4 are SSDN_OP_NOISE's (NS_* in elementwise.hip); 5 (NS_CROP in patch_pool.hip) is SSDN_OP_POOL_PATCH's crop and transform draw, which also reads stream 3 as SSDN_OP_NOISE does; PH_STREAM_POSTERIOR and above are the posterior sampler's.
 #pragma once
 
 struct Ph4 { unsigned v[4]; };

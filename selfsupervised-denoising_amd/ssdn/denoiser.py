@@ -320,6 +320,8 @@ class Denoiser(nn.Module):
                 if npv.data_ptr() == eng.noise_param.data_ptr():       # (denoise's "auto": the estimator has written the engine's tensor itself)
                     eng._np_src = None
                 elif not (getattr(npv, "_ssdn_const", False) and npv is getattr(eng, "_np_src", None)):
+                    if getattr(npv, "_ssdn_per_sample", False):        # (DevicePoolStream's per-image table: [B,C,1,1], one value per sample in every channel)
+                        npv = npv.reshape(B, -1)[:, 0]
                     eng.noise_param.copy_(npv.reshape(B).to(torch.float32), non_blocking=True)
                     eng._np_src = npv if getattr(npv, "_ssdn_const", False) else None
         else:
@@ -817,11 +819,20 @@ class Denoiser(nn.Module):
         `kind` with one kernel launch (SSDN_OP_METRICS: loss, PSNR of IMG_DENOISED and IMG_MU against the clean image over each
         sample's un-padded extent, noise / model std-dev x 255 -- what the reference trainer accumulates with ~20 ATen launches per
         step, train.py:205-218, utils/data.py:94-105).  Nothing is copied to the host; `read_metrics` does that when the trainer
-        prints.  per_sample=True returns {"psnr_out": [B], "psnr_mu_out": [B]} of this batch (host tensors: synchronises)."""
+        prints.  per_sample=True returns {"psnr_out": [B], "psnr_mu_out": [B]} of this batch (host tensors: synchronises).
+        A batch whose metadata has no Metadata.CLEAN (images that are already noisy) adds its loss and std-dev sums only: no PSNR sum or
+        count moves."""
         eng = self._last_engine
         if eng is None:
             raise RuntimeError("accumulate_metrics() needs a preceding run_pipeline()")
-        clean, ext, _ = self._clean_and_extent(data[NoisyDataset.METADATA])
+        meta = data[NoisyDataset.METADATA]
+        if not torch.is_tensor(meta.get(NoisyDataset.Metadata.CLEAN)):
+            # a batch of images that are already noisy (ssdn.datasets.DevicePoolStream): loss and the std-dev metrics only, no PSNR sum moves
+            if per_sample:
+                raise ValueError("accumulate_metrics(): the batch has no clean image (Metadata.CLEAN): there is no per-sample PSNR")
+            eng.accumulate_metrics(self._metrics_acc(kind), None, None, with_loss=with_loss and self._has_loss_last)
+            return None
+        clean, ext, _ = self._clean_and_extent(meta)
         eng.accumulate_metrics(self._metrics_acc(kind), clean, ext, with_loss=with_loss and self._has_loss_last)
         self._metrics_keep = (clean, ext)               # alive until the launch has run
         if per_sample:

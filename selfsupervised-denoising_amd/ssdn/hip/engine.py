@@ -478,23 +478,29 @@ class DenoiserEngine:
         return recs
 
     # ---- metrics (H11) -------------------------------------------------------------------------------------
-    def accumulate_metrics(self, acc: torch.Tensor, clean: torch.Tensor, ext: Optional[torch.Tensor] = None, with_loss: bool = True,
+    def accumulate_metrics(self, acc: torch.Tensor, clean: Optional[torch.Tensor], ext: Optional[torch.Tensor] = None, with_loss: bool = True,
                            stream=None):
         """Enqueue ONE launch that adds this batch's loss / PSNR(out) / PSNR(mu) / noise std / model std sums into `acc` (fp32 [16] on
         the device: sum, count per metric) -- the reference's per-step `Metric +=` lines (train.py:205-218).  clean: fp32 [B,C,H,W] on
-        the device; ext: int32 [B,2] valid extents of the two spatial axes (padded evaluation images) or None."""
+        the device; ext: int32 [B,2] valid extents of the two spatial axes (padded evaluation images) or None.
+        clean=None (a batch of images that are already noisy: there is no clean image): the kernel skips a metric whose source pointer is
+        null, so the two image outputs are withheld and no PSNR sum or count moves; `clean` is then any valid buffer, the engine's input."""
         a = self._metrics_args
         if a is None:
             a = self._metrics_args = L.MetricsArgs()
             a.B, a.C, a.H, a.W = self.B, self.C, self.H, self.W
             a.per = _ptr(self.metrics_per)
             if self.pipeline == "ssdn":
-                a.out, a.mu, a.model_std, a.noise_std = _ptr(self.pme), _ptr(self.mu), _ptr(self.model_std), _ptr(self.noise_std)
+                a.model_std, a.noise_std = _ptr(self.model_std), _ptr(self.noise_std)
                 # (gauss, impulse: one value per sample -- one for the whole batch when it is a learnt constant; poisson: per pixel)
                 a.noise_n = self.noise_std.numel() if self.style == "poisson" else (1 if self.mode == "const" else self.B)
-            else:
-                a.out = _ptr(self.main.tensor("out32"))
             self._metrics_ops = OpList([("metrics", a)])
+        if clean is None:
+            a.out, a.mu, clean = None, None, self.inp
+        elif self.pipeline == "ssdn":
+            a.out, a.mu = _ptr(self.pme), _ptr(self.mu)
+        else:
+            a.out = _ptr(self.main.tensor("out32"))
         if clean.dtype != torch.float32 or not clean.is_contiguous() or tuple(clean.shape) != (self.B, self.C, self.H, self.W):
             raise L.SsdnHipError("metrics: clean must be a contiguous fp32 [B,C,H,W] device tensor of the engine's shape")
         a.clean, a.acc = _ptr(clean), _ptr(acc)

@@ -18,7 +18,7 @@ OP = dict(pack_input=1, conv=2, pool_fwd=3, pool_bwd=4, upsum_bwd=5, unrot_fwd=6
           wpack=10, grad_pack=11, head_ssdn=12, head_final=13, spatial_mean=14, mse=15, mask_mse=16, adam=17,
           metrics=18, zero=19, event_record=20, noise=21, input_grad=22, head_vjp=23,
           mse_vjp=24, accum=25, head_posterior=26, ssim=27, calibration=28, image_in=29, image_out=30, noise_est=31,
-          tile_in=32, tile_out=33)
+          tile_in=32, tile_out=33, pool_patch=34)
 
 i32, f32, vp = C.c_int32, C.c_float, C.c_void_p
 
@@ -208,6 +208,12 @@ class TileOutArgs(C.Structure):
                 ("dst", vp), ("dst_bytes", C.c_int64)]
 
 
+class PoolPatchArgs(C.Structure):
+    _fields_ = [("pool", vp), ("offsets", vp), ("sizes", vp), ("params", vp), ("index", vp), ("noisy32", vp), ("ref32", vp), ("coords", vp),
+                ("param_out", vp), ("origin_out", vp), ("N", i32), ("B", i32), ("C", i32), ("P", i32), ("augment", i32),
+                ("n2v_box", i32), ("n2v_radius", i32), ("seed", C.c_uint64), ("offset", C.c_uint64)]
+
+
 def tile_count(n: int, T: int, O: int) -> int:
     """K(n) of include/ssdn_hip.h (SSDN_OP_TILE_IN): the T-sized tiles of overlap O along an image axis of n elements"""
     return 1 if n <= T else -(-(n - O) // (T - O))
@@ -219,7 +225,7 @@ ARG_TYPES = dict(pack_input=PackInputArgs, conv=ConvArgs, pool_fwd=PoolArgs, poo
                  mse=MseArgs, mask_mse=MseArgs, adam=AdamArgs, metrics=MetricsArgs, zero=ZeroArgs, event_record=EventArgs, noise=NoiseArgs,
                  input_grad=InputGradArgs, head_vjp=HeadVjpArgs, mse_vjp=MseVjpArgs, accum=AccumArgs,
                  head_posterior=HeadPosteriorArgs, ssim=SsimArgs, calibration=CalibrationArgs, image_in=ImageInArgs, image_out=ImageOutArgs,
-                 noise_est=NoiseEstArgs, tile_in=TileInArgs, tile_out=TileOutArgs)
+                 noise_est=NoiseEstArgs, tile_in=TileInArgs, tile_out=TileOutArgs, pool_patch=PoolPatchArgs)
 
 # every symbol include/ssdn_hip.h declares
 ABI_VERSION = 19      # SSDN_ABI_VERSION of include/ssdn_hip.h this binding mirrors

@@ -37,10 +37,11 @@ from torch.utils.data import DataLoader
 import ssdn
 from ssdn.cfg import DEFAULT_RUN_DIR
 from ssdn.datasets import CleanPatches, DevicePatchStream, FixedLengthSampler, HDF5Dataset, NoisyDataset, SamplingOrder, UnlabelledImageFolderDataset
+from ssdn.datasets.device_pool import DEFAULT_POOL_BYTES, POOL_ALGORITHMS, DevicePoolStream, ImagePool
 from ssdn.datasets.transforms import RandomCrop
 from ssdn.denoiser import Denoiser
 from ssdn.models import NoiseNetwork
-from ssdn.params import ConfigValue, DatasetType, HistoryValue, Pipeline, PipelineOutput, StateValue
+from ssdn.params import ConfigValue, DatasetType, HistoryValue, NoiseAlgorithm, NoiseValue, Pipeline, PipelineOutput, StateValue
 from ssdn.utils import Metric, MetricDict, TrackedTime, separator
 
 logger = logging.getLogger("ssdn.train")
@@ -49,6 +50,44 @@ _CALIB_CACHE = "_calibration_per_sample"  # ... and of the per-sample calibratio
 _POSTERIOR_COV = "_posterior_cov"         # (an output dict may bring the posterior covariance [B, C(C+1)/2, H, W] along: the path without a GPU)
 CALIB_METRICS = ("nll", "maha", "rmse_ratio", "cover_2s")     # what an evaluation reports as calib_<name>
 _PSNR_CACHE = "_psnr_per_sample"         # key of the per-sample PSNR values the device metric kernel produced for an output dict
+
+
+NOISY_MODES = ("style", "auto")
+
+
+def check_noisy(cfg: Dict, noisy: Optional[str], augment: bool = False, pool_bytes: Optional[int] = None):
+    """Training on images that are already noisy (`DenoiserTrainer.noisy`, `--noisy`): ValueError, with what to do instead, for every
+    combination that cannot work.  noisy: None (off), "style" (the images carry the corruption NOISE_STYLE describes, its number is the
+    known parameter) or "auto" (the parameter of every image is estimated once, when the pool is built)."""
+    from ssdn.utils import noise
+    if not noisy:
+        if augment:
+            raise ValueError("--augment transforms the patches of the noisy-image pool: it needs --noisy")
+        if pool_bytes is not None:
+            raise ValueError("--pool_gb sizes the noisy-image pool: it needs --noisy")
+        return
+    if noisy not in NOISY_MODES:
+        raise ValueError("noisy must be one of %s, got %r" % (", ".join(NOISY_MODES), noisy))
+    if pool_bytes is not None and pool_bytes <= 0:
+        raise ValueError("--pool_gb must be positive")
+    algo, style = cfg[ConfigValue.ALGORITHM], cfg[ConfigValue.NOISE_STYLE]
+    if algo not in POOL_ALGORITHMS:
+        raise ValueError("--noisy: %s needs a clean image or a second realisation of every training image; train ssdn, ssdn_u_only or n2v "
+                         "on images that are already noisy, or give clean images and drop --noisy" % algo.value)
+    kind, params, _ = noise.parse_style(style)
+    known = algo == NoiseAlgorithm.SELFSUPERVISED_DENOISING and cfg.get(ConfigValue.NOISE_VALUE) == NoiseValue.KNOWN
+    if noisy == "auto":
+        if kind not in ("gauss", "poisson"):
+            raise ValueError("--noisy auto: no noise-level estimator exists for %s noise; use --noisy with the style's own parameter" % kind)
+        if not known:
+            raise ValueError("--noisy auto estimates the noise parameter an ssdn model with --noise_value known reads; this configuration "
+                             "reads none: use plain --noisy")
+    elif known and len(params) > 1:
+        raise ValueError("--noisy: the ranged style %s says nothing about one image's noise level, which --noise_value known needs; use "
+                         "--noisy auto to estimate it per image, or a single-valued style" % style)
+    if cfg[ConfigValue.TRAIN_PATCH_SIZE] % NoiseNetwork.input_wh_mul():
+        raise ValueError("--noisy: the patch size must be a multiple of %d (patches go to the network as they are cut), got %d"
+                         % (NoiseNetwork.input_wh_mul(), cfg[ConfigValue.TRAIN_PATCH_SIZE]))
 
 
 class _RankShard(torch.utils.data.Sampler):
@@ -114,6 +153,12 @@ class DenoiserTrainer:
         # calib_rmse_ratio, calib_cover_2s.  calibration_hist: the z-score histogram [C,34] summed over the last such evaluation
         self.calibration = False
         self.calibration_hist = None
+        # the training images are ALREADY noisy (`--noisy`): None, "style" or "auto" (check_noisy); the minibatches then come out of a
+        # device-resident pool (ssdn.datasets.device_pool), `augment` switches its dihedral transform on, `pool_bytes` (None: the module's
+        # default) caps it.  Plain attributes: they travel as the extra top-level key "noisy" of a `.training` file, only when the mode is on
+        self.noisy: Optional[str] = None
+        self.augment = False
+        self.pool_bytes: Optional[int] = None
 
     # ---- target -----------------------------------------------------------------------------------------------------------
     @property
@@ -232,7 +277,9 @@ class DenoiserTrainer:
                 denoiser.train()
                 # H11: on a GPU the step's metric sums stay on the device (one kernel inside train_step, SSDN_OP_METRICS) and come to the
                 # host when the trainer prints; the reference's per-step tensor arithmetic (train.py:205-218) is the CPU path
-                on_device = getattr(denoiser, "device", torch.device("cpu")).type == "cuda" and torch.is_tensor(data[NoisyDataset.METADATA].get(MD.CLEAN))
+                # (a minibatch of images that are already noisy has no clean image: its loss and std-dev sums stay on the device all the same)
+                has_clean = not self.noisy and torch.is_tensor(data[NoisyDataset.METADATA].get(MD.CLEAN))
+                on_device = getattr(denoiser, "device", torch.device("cpu")).type == "cuda" and (has_clean or bool(self.noisy))
                 if k + 1 < group:          # (no exchange, no optimiser step: the group's last minibatch does both, once)
                     outputs = denoiser.accumulate_step(data, **({"metrics": True} if on_device else {}))
                 else:
@@ -241,7 +288,7 @@ class DenoiserTrainer:
                 if not on_device:
                     with torch.no_grad():
                         train_history["loss"] += outputs[PipelineOutput.LOSS]
-                        for key, name in self.img_outputs(prefix="psnr").items():
+                        for key, name in self.img_outputs(prefix="psnr").items() if has_clean or not self.noisy else ():
                             train_history[name] += self.calculate_psnr(outputs, key, False)
                         for key in (PipelineOutput.NOISE_STD_DEV, PipelineOutput.MODEL_STD_DEV):
                             if key in outputs:
@@ -505,8 +552,10 @@ class DenoiserTrainer:
               "optimizer": self.denoiser.optimizer_state_dict(self.learning_rate), "rng": torch.get_rng_state()}
         # (an extra key the reference's loader ignores) the device patch stream's Philox key and minibatch counter: a resumed run
         # continues the noise stream instead of restarting it at offset 0 under a re-drawn key
-        if isinstance(self.trainloader, DevicePatchStream):
+        if isinstance(self.trainloader, (DevicePatchStream, DevicePoolStream)):
             sd["device_stream"] = self.trainloader.state_dict()
+        if self.noisy:                           # (an ordinary run's file keeps the key set it always had)
+            sd["noisy"] = {"mode": self.noisy, "augment": bool(self.augment), "pool_bytes": self.pool_bytes}
         if int(self.accumulate) > 1:             # (a K = 1 file keeps the key set it always had)
             sd["accumulate"] = int(self.accumulate)
         return sd
@@ -521,6 +570,8 @@ class DenoiserTrainer:
         self.denoiser.load_optimizer_state_dict(state_dict["optimizer"])
         self._stream_state = state_dict.get("device_stream")
         self.accumulate = int(state_dict.get("accumulate", 1))
+        noisy = state_dict.get("noisy") or {}
+        self.noisy, self.augment, self.pool_bytes = noisy.get("mode"), bool(noisy.get("augment", False)), noisy.get("pool_bytes")
         torch.set_rng_state(state_dict["rng"])
         if self.world > 1 and self.rank > 0:
             # the file holds rank 0's generator state: the other ranks continue from a state derived from it, not from a copy
@@ -535,13 +586,10 @@ class DenoiserTrainer:
             return HDF5Dataset(path, transform=transform, channels=ch)
         raise NotImplementedError("Dataset type not implemented")
 
-    def train_data(self) -> Tuple[DataLoader, NoisyDataset, FixedLengthSampler]:
+    def _train_sampler(self, dataset) -> FixedLengthSampler:
+        """The sampling order of a training run over `dataset` (only its length is read): continued from a loaded `.training` file,
+        the same global order on every rank of a job, whose rows `self._shard` then deals out (None in a single process)."""
         cfg = self.cfg
-        crop = RandomCrop(cfg[ConfigValue.TRAIN_PATCH_SIZE], pad_if_needed=True, padding_mode="reflect")
-        dataset = NoisyDataset(self._open(cfg[ConfigValue.TRAIN_DATA_PATH], cfg[ConfigValue.TRAIN_DATASET_TYPE], crop),
-                               cfg[ConfigValue.NOISE_STYLE], cfg[ConfigValue.ALGORITHM], pad_uniform=False,
-                               pad_multiple=NoiseNetwork.input_wh_mul(), square=cfg[ConfigValue.BLINDSPOT], training_mode=True)
-        _ = dataset[0]
         if self.world > 1:
             g = torch.get_rng_state()
             torch.manual_seed(1234 + self.state.get(StateValue.ITERATION, 0))      # the same global order on every rank
@@ -554,6 +602,56 @@ class DenoiserTrainer:
                 order = SamplingOrder(list(order.order) + list(extra.sampler()), order.index)
             sampler.for_next_iter(order)
             self._train_iter = None
+        if self.world > 1:
+            _ = iter(sampler)                        # materialise the order under the common seed, then reuse it
+            sampler.for_next_iter(sampler.last_iter())
+            torch.set_rng_state(g)
+            self._shard = _RankShard(sampler, cfg[ConfigValue.TRAIN_MINIBATCH_SIZE], self.rank, self.world)
+        else:
+            self._shard = None
+        return sampler
+
+    def _noisy_train_data(self):
+        """`train_data` for images that are already noisy: the folder or HDF5 file is decoded once into a device-resident pool
+        (ssdn.datasets.ImagePool; every rank of a job holds all of it) and the minibatches are cut out of it by one launch each
+        (DevicePoolStream): no DataLoader, no workers.  Without a GPU the same stream runs through torch."""
+        from ssdn.utils import noise
+        cfg = self.cfg
+        check_noisy(cfg, self.noisy, self.augment, self.pool_bytes)
+        child = self._open(cfg[ConfigValue.TRAIN_DATA_PATH], cfg[ConfigValue.TRAIN_DATASET_TYPE], None)
+        dev = self.denoiser.device if self.denoiser is not None and hasattr(self.denoiser, "device") else \
+            torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        pool = ImagePool(child, dev, DEFAULT_POOL_BYTES if self.pool_bytes is None else int(self.pool_bytes))
+        logger.info("Noisy-image pool: %d images, %.1f MB on %s" % (len(pool), pool.nbytes / 1e6, dev))
+        if self.noisy == "auto":
+            if self.denoiser is None or torch.device(dev).type != "cuda":
+                raise ValueError("--noisy auto estimates the noise levels on the device: it needs a GPU and the trainer's target")
+            pool.estimate_params(self.denoiser, noise.parse_style(cfg[ConfigValue.NOISE_STYLE])[0])
+            logger.info("Estimated noise parameters: min %.4g, median %.4g, max %.4g" % (
+                float(pool.params_host.min()), float(pool.params_host.median()), float(pool.params_host.max())))
+        sampler = self._train_sampler(pool)
+        batches = self._shard if self._shard is not None else \
+            torch.utils.data.BatchSampler(sampler, cfg[ConfigValue.TRAIN_MINIBATCH_SIZE], drop_last=False)
+        stream = DevicePoolStream(pool, batches, cfg[ConfigValue.ALGORITHM], cfg[ConfigValue.NOISE_STYLE], cfg[ConfigValue.TRAIN_PATCH_SIZE],
+                                  augment=self.augment, per_image=self.noisy == "auto", rank=self.rank)
+        if getattr(self, "_stream_state", None):
+            stream.load_state_dict(self._stream_state, rank=self.rank)
+            self._stream_state = None
+        if self.denoiser is not None and self.denoiser.device.type == "cuda":
+            stream.attach(self.denoiser)
+        return stream, child, sampler
+
+    def train_data(self) -> Tuple[DataLoader, NoisyDataset, FixedLengthSampler]:
+        cfg = self.cfg
+        if self.noisy:
+            return self._noisy_train_data()
+        check_noisy(cfg, None, self.augment, self.pool_bytes)
+        crop = RandomCrop(cfg[ConfigValue.TRAIN_PATCH_SIZE], pad_if_needed=True, padding_mode="reflect")
+        dataset = NoisyDataset(self._open(cfg[ConfigValue.TRAIN_DATA_PATH], cfg[ConfigValue.TRAIN_DATASET_TYPE], crop),
+                               cfg[ConfigValue.NOISE_STYLE], cfg[ConfigValue.ALGORITHM], pad_uniform=False,
+                               pad_multiple=NoiseNetwork.input_wh_mul(), square=cfg[ConfigValue.BLINDSPOT], training_mode=True)
+        _ = dataset[0]
+        sampler = self._train_sampler(dataset)
         kw = dict(num_workers=cfg[ConfigValue.DATALOADER_WORKERS], pin_memory=cfg[ConfigValue.PIN_DATA_MEMORY] or torch.cuda.is_available())
         # N2: on a GPU the workers ship the clean patch as uint8 and the per-sample noise / Noise2Void manipulation / metadata
         # are produced for the whole minibatch on the device (ssdn.datasets.device_stream); SSDN_HOST_DATA=1 keeps the
@@ -565,13 +663,8 @@ class DenoiserTrainer:
         if device_stream:
             kw["collate_fn"] = CleanPatches.collate          # (the workers deliver whole minibatches: CleanPatches.__getitems__)
         if self.world > 1:
-            _ = iter(sampler)                        # materialise the order under the common seed, then reuse it
-            sampler.for_next_iter(sampler.last_iter())
-            torch.set_rng_state(g)
-            self._shard = _RankShard(sampler, cfg[ConfigValue.TRAIN_MINIBATCH_SIZE], self.rank, self.world)
             loader = DataLoader(source, batch_sampler=self._shard, **kw)
         else:
-            self._shard = None
             loader = DataLoader(source, sampler=sampler, batch_size=cfg[ConfigValue.TRAIN_MINIBATCH_SIZE], **kw)
         if device_stream:
             dev = self.denoiser.device if self.denoiser is not None and hasattr(self.denoiser, "device") else \
