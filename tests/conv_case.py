@@ -7,8 +7,14 @@ fp32 in any order, so that the expected output is an integer that does not depen
 equality (check_ints).  device=False builds the operands and the argument struct without a GPU (the pointers are placeholders): the
 host-side queries of the library and the reference need no more.
 
+The 1x1 layers (one tap; k_gdma, csrc/gemm_dma.hip) have more: the fused SSDN_OP_UNROT_BWD (unrot=True: the output goes, un-rotated and
+times LeakyReLU' of unrot_mask, to `unrot`), a second, narrow 1x1 layer behind the first (next=dict(M4, bias, act): two SSDN_OP_CONV
+records in one list, fp32 NCHW output), and under ints=True the LeakyReLU and masks of both signs -- what follows the exact integer sum is
+a fixed chain of fp32 operations and one round-to-nearest-even conversion, which ints_expected() repeats in torch float32.
+
 Used by tests/test_hip_conv16.py (k_conv16 against k_conv), tests/test_hip_cdma_walk.py / tests/test_cdma_walk_cpu.py (k_cdma's tile
-walk) and tests/test_hip_conv_route.py (one launch per kernel of SSDN_OP_CONV; the 1x1 layers are its only tap sets of another length)."""
+walk), tests/test_hip_conv_route.py (one launch per kernel of SSDN_OP_CONV) and tests/test_hip_gdma_walk.py / tests/test_gdma_walk_cpu.py
+(k_gdma's tile walk and epilogues)."""
 import ctypes as C
 
 import torch
@@ -17,6 +23,7 @@ SLOPE = 0.1
 INT_NNZ = 32        # +-1 entries per weight row of the integer operands (see Case._int_operands for the bound this gives)
 INT_IN, INT_BIAS, INT_ADD = 2, 4, 8      # |input|, |bias|, |addend| of the integer operands
 INT_LIMIT = 256     # integers up to here are exact in bf16 (8 significant bits) and in fp16 (11)
+NEXT_GUARD = 256    # fp32 elements in front of and behind the second layer's output that must stay NaN
 
 
 def _dev():
@@ -48,6 +55,13 @@ def unrot(y, B, fill):
     return torch.cat([Interp._rot(s[r * B:(r + 1) * B], a) for r, a in enumerate((0, 270, 180, 90))], -1)
 
 
+def unrot_bwd(u, C_):
+    """the adjoint of unrot(): SSDN_OP_UNROT_BWD of include/ssdn_hip.h without its mask, u [B,P,P,4C] -> [4B,P,P,C]; row P-1, which the
+    shift cut off, holds zeros"""
+    y = unrot_back(u, C_)
+    return torch.cat([y, torch.zeros_like(y[:, :1])], 1)
+
+
 def unrot_back(u, C_):
     """the rows y <= P-2 of the tensor [4B,P,P,C] whose un-rotation u [B,P,P,4C] is -> [4B,P-1,P,C]"""
     from interp import Interp
@@ -61,11 +75,11 @@ class Case:
 
     def __init__(self, role, N, c0, c1, up0, M, taps, H=16, W=16, mask=False, add=False, upsum_c=0, bias=None, seed=0, dst32=False,
                  edge=False, cm=False, ints=False, sign_out=False, mask_sign=False, upsum_mask_sign=False, urot=False, urot_smask=False,
-                 kreal=0, device=True):
+                 kreal=0, device=True, unrot=False, unrot_smask=False, next=None):
         from ssdn.hip.graph import choose_conv_tile
         L, lib = _lib()
         self.role, self.N, self.H, self.W, self.c0, self.c1, self.up0, self.M, self.upsum_c = role, N, H, W, c0, c1, up0, M, upsum_c
-        self.ints, self.device, self.urot = ints, device, urot
+        self.ints, self.device, self.urot, self.unrot, self.next = ints, device, urot, unrot, next
         bf = role == "dgrad"
         self.dt = torch.bfloat16 if bf else torch.float16
         self.taps = [(-dy, -dx) for dy, dx in taps] if bf else list(taps)      # the data gradient walks the mirrored window
@@ -131,6 +145,10 @@ class Case:
             self.mask = _rand(gen, (N, H, W, M)).to(torch.float16) if mask else None
             self.add = _rand(gen, (N, H, W, M)).to(self.dt) if add else None
             self.umask = _rand(gen, (N, H // 2, W // 2, upsum_c)).to(torch.float16) if upsum_c else None
+        # (the operands of the 1x1 layers' extras are drawn behind everything else: the callers without them get what they always got)
+        self.unrot_mask = _rand(gen, (4 * N, H, W, M // 4)).to(torch.float16) if unrot else None
+        if next is not None:
+            self._next_operands(gen, next)
         self.dw = self.w.to(_dev()) if device else None
         self.dbias = self.bias.to(_dev()) if self.bias is not None and device else None
 
@@ -145,7 +163,9 @@ class Case:
         a.w, a.M, a.Mpad, a.Ktot = (self.dw.data_ptr() if device else 0x1000), M, self.Mpad, self.Ktot
         if self.bias is not None:
             a.bias = self.dbias.data_ptr() if device else 0x1000
-        a.act = int(not bf and not ints)          # (the integer operands: no LeakyReLU)
+        # (the integer operands: no LeakyReLU -- but for a 1x1 layer, whose expectation follows the fp32 chain behind the sum; in front of a
+        # second layer the tile must hold integers)
+        a.act = int(not bf and (not ints or (len(self.taps) == 1 and next is None)))
         if mask:
             _, a.mask = view(self.mask, window=not mask_sign)
             if mask_sign:
@@ -165,6 +185,18 @@ class Case:
                 a.urot_smask = self._bytes("urot_smask", (N, H, W, M // 8))
         else:
             self.outs["dst"], a.dst = view(torch.zeros(N, H, W, M, dtype=self.dt))
+        if unrot:
+            # the conv's N is the batch: the output channel block r of image b belongs to image r N + b of the rotated stack
+            self.outs["unrot"], a.unrot = view(torch.zeros(4 * N, H, W, M // 4, dtype=self.dt))
+            if unrot_smask:
+                # the bytes SSDN_OP_UNROT_FWD writes (oracle/interp.py): 12 per pixel, the cut-off row P-1 untouched; the activation
+                # itself must then not be read: it holds NaN, which the kernel's sign test would take for "positive"
+                sb = pack_signs(self.unrot_mask.float())
+                sb[:, -1] = 0xA5
+                a.unrot_smask = raw(sb)
+                _, a.unrot_mask = view(torch.full_like(self.unrot_mask, float("nan")))
+            else:
+                _, a.unrot_mask = view(self.unrot_mask)
         if sign_out:
             a.sign_out = self._bytes("sign_out", (N, H, W, M // 8))
         if upsum_c:
@@ -187,6 +219,37 @@ class Case:
             self.dwc = wc.to(_dev()) if device else None
             a.wc = self.dwc.data_ptr() if device else 0x1000
         self.a = a
+        if next is not None:
+            a4 = L.ConvArgs()
+            a4.src0 = L.View(a.dst.p, a.dst.cs, a.dst.co)
+            a4.c0, a4.c1, a4.up0, a4.N, a4.H, a4.W, a4.ntaps = M, 0, 0, N, H, W, 1
+            self.dw4 = self.w4.to(_dev()) if device else None
+            self.dbias4 = self.bias4.to(_dev()) if self.bias4 is not None and device else None
+            a4.w, a4.M, a4.Mpad, a4.Ktot = (self.dw4.data_ptr() if device else 0x1000), next["M4"], 32, M
+            if self.bias4 is not None:
+                a4.bias = self.dbias4.data_ptr() if device else 0x1000
+            a4.act = int(bool(next.get("act")))
+            self.next_n = N * next["M4"] * H * W
+            self.next_buf = torch.empty(self.next_n + 2 * NEXT_GUARD, device=_dev()) if device else None
+            a4.dst32 = self.next_buf.data_ptr() + 4 * NEXT_GUARD if device else 0x1000
+            a4.ltw, a4.lth, a4.ltn, a4.kc = choose_conv_tile(N, H, W, self.taps, M, 32, out16=False, cus=cus if cus > 0 else 256)
+            a4.bf16, a4.kreal = 0, M
+            self.a4 = a4
+
+    def _next_operands(self, gen, next):
+        """the second layer's weights [1][32][M] (rows >= M4: zeros) and bias.  Integer operands: INT_NNZ entries +-1 per row and a bias in
+        {-4..4} on the first layer's integers (no activation there: |.| <= 2 INT_NNZ + 4 = 68), so |out| <= 32 * 68 + 4 -- exact in fp32"""
+        M4 = next["M4"]
+        if self.ints:
+            w4 = torch.zeros(1, 32, self.M)
+            for m in range(M4):
+                w4[0, m, torch.randperm(self.M, generator=gen)[:INT_NNZ]] = torch.randint(0, 2, (INT_NNZ,), generator=gen).float() * 2 - 1
+            b4 = _randint(gen, (M4,), INT_BIAS)
+        else:
+            w4 = _rand(gen, (1, 32, self.M), 1.0 / (3.0 * self.M ** 0.5))
+            w4[:, M4:] = 0
+            b4 = _rand(gen, (M4,), 0.3)
+        self.w4, self.bias4 = w4.to(torch.float16), (b4 if next.get("bias") else None)
 
     def _bytes(self, name, shape):
         if not self.device:
@@ -196,24 +259,28 @@ class Case:
 
     def _int_operands(self, gen, bias, mask, add, hs, ws):
         """Integer operands.  Inputs dense in {-2..2}; each output channel's weight row has INT_NNZ entries +-1 at hashed (tap, channel)
-        positions -- row m takes positions m INT_NNZ .. (m + 1) INT_NNZ - 1 (mod 9 Ktot) of one hashed permutation of all positions, so
-        the rows differ and every position is hit by floor or ceil(M INT_NNZ / 9 Ktot) rows; bias in {-4..4}, addend in {-8..8}; the masks
-        are positive (factor exactly 1: the launch keeps its mask operand and so its kernel instantiation).  Worst case
-        |v| <= 2 INT_NNZ + 4 + 8 = 76 and a fused 2x2 up-sum (no bias, mask or addend there) <= 4 * 2 INT_NNZ = 256 = INT_LIMIT."""
+        positions -- row m takes positions m INT_NNZ .. (m + 1) INT_NNZ - 1 (mod ntaps Ktot) of one hashed permutation of all positions, so
+        the rows differ and every position is hit by floor or ceil(M INT_NNZ / (ntaps Ktot)) rows; bias in {-4..4}, addend in {-8..8}; the masks
+        are positive (factor exactly 1: the launch keeps its mask operand and so its kernel instantiation) -- but for a 1x1 layer, whose
+        masks take both signs.  Worst case |v| <= 2 INT_NNZ + 4 + 8 = 76 and a fused 2x2 up-sum (no bias, mask or addend there)
+        <= 4 * 2 INT_NNZ = 256 = INT_LIMIT; one tap (Ktot >= INT_NNZ, no addend): |v| <= 2 INT_NNZ + 4 = 68."""
         N, H, W, M, Ktot = self.N, self.H, self.W, self.M, self.Ktot
         bf = self.role == "dgrad"
         s0 = _randint(gen, (N, hs, ws, self.c0), INT_IN) if self.c0 else None
         s1 = _randint(gen, (N, H, W, self.c1), INT_IN) if self.c1 else None
-        P = 9 * Ktot
+        ntaps = len(self.taps)
+        P = ntaps * Ktot
         assert INT_NNZ <= P
         perm = torch.randperm(P, generator=gen)
         pos = perm[(torch.arange(M)[:, None] * INT_NNZ + torch.arange(INT_NNZ)[None, :]) % P]        # [M][INT_NNZ] -> tap * Ktot + k
         sign = torch.randint(0, 2, (M, INT_NNZ), generator=gen).float() * 2 - 1
-        w = torch.zeros(9, self.Mpad, Ktot)
+        w = torch.zeros(ntaps, self.Mpad, Ktot)
         w[pos // Ktot, torch.arange(M)[:, None].expand_as(pos), pos % Ktot] = sign
         self.w_hits = torch.bincount(pos.reshape(-1), minlength=P)                                  # rows per (tap, channel) position
         bias_t = _randint(gen, (M,), INT_BIAS) if (bias if bias is not None else not bf) else None
         mask_t = (torch.rand((N, H, W, M), generator=gen) + 0.5).to(torch.float16) if mask else None
+        if mask and ntaps == 1:        # a 1x1 layer: both signs (ints_expected follows the epilogue's fp32 chain)
+            mask_t = ((mask_t.float() - 1.0) * 2).to(torch.float16)
         add_t = _randint(gen, (N, H, W, M), INT_ADD).to(self.dt) if add else None
         umask_t = (torch.rand((N, H // 2, W // 2, self.upsum_c), generator=gen) + 0.5).to(torch.float16) if self.upsum_c else None
         return s0, s1, w, bias_t, mask_t, add_t, umask_t
@@ -231,16 +298,20 @@ class Case:
         return rc, dict(zip(("tiles_x", "tiles_y", "segs", "tps", "nitems", "grid", "xcd_map", "mt_blocks"), out))
 
     def launch(self):
-        """the launch from poisoned outputs -> {name: the whole (wide) output tensor}, on the host"""
+        """the launch (with next: the two records in one list) from poisoned outputs -> {name: the whole (wide) output tensor}, on the host"""
         from ssdn.hip.engine import OpList, current_stream
         for t in self.outs.values():
             t.fill_(float("nan"))
         for t in self.bytes_out.values():
             t.fill_(0xA5)
-        OpList([("conv", self.a)]).run(current_stream())
+        if self.next is not None:
+            self.next_buf.fill_(float("nan"))
+        OpList([("conv", self.a)] + ([("conv", self.a4)] if self.next is not None else [])).run(current_stream())
         torch.cuda.synchronize()
         got = {k: t.detach().cpu().clone() for k, t in self.outs.items()}
         got.update({k: t.detach().cpu().clone() for k, t in self.bytes_out.items()})
+        if self.next is not None:
+            got["next32"] = self.next_buf.detach().cpu().clone()       # (with its guards)
         return got
 
     def run(self, roles):
@@ -277,8 +348,12 @@ class Case:
             v += torch.einsum("nyxk,mk->nyxm", xp[:, 2 + dy:2 + dy + H, 2 + dx:2 + dx + W], w[t, :self.M])
         if self.bias is not None:
             v += to(self.bias).double()
+        self.pre = v.clone()           # the sum itself: what ints_expected's fp32 chain of a 1x1 layer starts from
         if self.a.act:
             v = torch.where(v > 0, v, SLOPE * v)
+        if self.unrot:
+            # fused SSDN_OP_UNROT_BWD: everything below is in the rotated stack's place [4N,P,P,M/4]
+            self.pre, v = unrot_bwd(self.pre, self.M // 4), unrot_bwd(v, self.M // 4) * torch.where(to(self.unrot_mask).double() > 0, 1.0, SLOPE)
         conv = v.clone()
         if self.add is not None:
             v = v + to(self.add).double()
@@ -292,11 +367,59 @@ class Case:
             self.up_abs = (u[:, 0::2, 0::2].abs() + u[:, 0::2, 1::2].abs() + u[:, 1::2, 0::2].abs() + u[:, 1::2, 1::2].abs()) * g
         return v, up, conv
 
+    def next_ref64(self, first, dev=None, act=True):
+        """the second layer in float64 on `first` [N,H,W,M], the first layer's rounded 16-bit output -> [N,M4,H,W]; act=False: without
+        its activation"""
+        to = (lambda t: t.to(dev)) if dev is not None else (lambda t: t)
+        M4 = self.next["M4"]
+        v = torch.einsum("nyxk,mk->nmyx", to(first).double(), to(self.w4).double()[0, :M4])
+        if self.bias4 is not None:
+            v += to(self.bias4).double()[None, :, None, None]
+        return torch.where(v > 0, v, SLOPE * v) if self.a4.act and act else v
+
+    def _ints_chain(self, dev=None):
+        """a 1x1 layer's integer expectation.  The sum v is an exact integer in any order; what k_gdma does behind it is a fixed chain
+        of fp32 operations and round-to-nearest-even conversions, repeated here in torch float32: forward max(v, 0.1f v) -> fp16;
+        data gradient bf16(v), then * (mask > 0 ? 1 : 0.1f) -> bf16 (the fused un-rotation: the same on unrot_mask, zeros in row P-1);
+        a second layer: its exact integer sum + bias in fp32, v > 0 ? v : 0.1f v."""
+        self.ref64(dev)
+        pre = self.pre
+        assert bool((pre == pre.round()).all()) and float(pre.abs().max()) <= INT_LIMIT, "integer reference: |v| max %g" % float(pre.abs().max())
+        slope = torch.tensor(SLOPE, dtype=torch.float32, device=pre.device)
+        one = torch.ones((), dtype=torch.float32, device=pre.device)
+        x = pre.float() + 0.0
+        if self.a.act:
+            x = torch.maximum(x, x * slope)
+        x = x.to(self.dt)
+        mask = self.unrot_mask if self.unrot else self.mask
+        if mask is not None:
+            x = (x.float() * torch.where(mask.to(pre.device).float() > 0, one, slope)).to(self.dt)
+
+        def wide(t):
+            o = torch.full(t.shape[:-1] + (t.shape[-1] + 16,), float("nan"), dtype=self.dt, device=t.device)
+            o[..., 8:8 + t.shape[-1]] = t
+            return o
+        if self.unrot:      # nothing goes to dst
+            return {"unrot": wide(x), "dst": torch.full((self.N, self.H, self.W, self.M + 16), float("nan"), dtype=self.dt, device=x.device)}
+        out = {"dst": wide(x)}
+        if self.next is not None:
+            y = self.next_ref64(x, dev, act=False)
+            assert bool((y == y.round()).all()) and float(y.abs().max()) <= INT_NNZ * (2 * INT_NNZ + INT_BIAS) + INT_BIAS
+            y = y.float() + 0.0
+            if self.a4.act:
+                y = torch.where(y > 0, y, y * slope)
+            buf = torch.full((self.next_n + 2 * NEXT_GUARD,), float("nan"), dtype=torch.float32, device=y.device)
+            buf[NEXT_GUARD:NEXT_GUARD + self.next_n] = y.reshape(-1)
+            out["next32"] = buf
+        return out
+
     def ints_expected(self, dev=None):
         """the integer operands' expected outputs {name: the whole wide tensor, NaN where the launch stores nothing}, after asserting the
         condition that makes them exact in any accumulation order and in the 16-bit output type: every value, fused 2x2 up-sums included,
         is an integer of magnitude <= INT_LIMIT"""
         assert self.ints
+        if len(self.taps) == 1:
+            return self._ints_chain(dev)
         ref, up, _ = self.ref64(dev)
         for r in (ref, up):
             if r is not None:
@@ -346,6 +469,9 @@ def _check_ref(case, got, sparse=False, dev=None):
         scale = torch.where(mask.double() > 0, 1.0, SLOPE) if mask is not None else 1.0
         tol = tol + ulp * (add.double().abs() + conv.abs()) * scale
     key, Mw = "dst", M
+    if case.unrot:      # fused UNROT_BWD: ref64 answers in the rotated stack's place; the whole window is written and dst is not touched
+        key, Mw = "unrot", M // 4
+        assert bool(torch.isnan(got["dst"].float()).all()), "the fused un-rotation stored to dst"
     if case.urot:
         key, Mw, B = "urot", 4 * M, case.N // 4
         ref, tol = unrot(ref, B, float("nan")), unrot(tol, B, 0.0)
@@ -372,6 +498,22 @@ def _check_ref(case, got, sparse=False, dev=None):
         print("  fused up-sum: max err / bound %.4f" % float((erru / tolu).max()))
         assert bool((erru <= tolu).all()), "upsum: %d elements beyond the bound" % int((erru > tolu).sum())
         assert bool(torch.isnan(got["upsum"][..., :8].float()).all()) and bool(torch.isnan(got["upsum"][..., 8 + uc:].float()).all())
+
+
+def _check_next32(case, got, dev=None):
+    """the second layer's fp32 NCHW output against float64 on the first layer's own stored 16-bit output: the forward bound of _check_ref
+    (as tests/test_hip_conv_route.py::_check_dst32); the guards in front of and behind it are still NaN"""
+    if dev is not None:
+        got = {k: v.to(dev) for k, v in got.items()}
+    ref = case.next_ref64(got["dst"][..., 8:8 + case.M], dev).reshape(-1)
+    tol = 2e-3 * ref.abs() + 2e-3 * float(ref.abs().max()) * 1e-2 + 1e-9
+    buf = got["next32"]
+    g = buf[NEXT_GUARD:NEXT_GUARD + case.next_n].double()
+    assert bool(torch.isfinite(g).all())
+    err = (g - ref).abs()
+    print("  second layer M4 %d: max err / bound %.4f" % (case.next["M4"], float((err / tol).max())))
+    assert bool((err <= tol).all()), "next32: %d elements beyond the bound, max err %.3e" % (int((err > tol).sum()), float(err.max()))
+    assert bool(torch.isnan(buf[:NEXT_GUARD]).all()) and bool(torch.isnan(buf[NEXT_GUARD + case.next_n:]).all()), "stored outside the output"
 
 
 def check_ints(case, got, dev=None):
