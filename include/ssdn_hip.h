@@ -905,6 +905,13 @@ int ssdn_wgrad_variant(const ssdn_wgrad_args* a, int32_t* out9);
  * under the current ssdn_conv_set_mode, 0 if another kernel serves it (out8 is then what k_cdma would have done), < 0 on invalid
  * arguments.  (planner / test aid) */
 int ssdn_conv_dma_split(const ssdn_conv_args* a, int32_t* out8);
+/* The k_conv launches (csrc/conv_mfma.hip) SSDN_OP_CONV with these arguments makes under the current ssdn_conv_set_mode / _set_conv16:
+ * returns their number (1 or 2: the blocks of 96 output channels, then the tail of 64 or 32), 0 if the route gives the op to another
+ * kernel, < 0 with a message on invalid arguments (what the launch itself would refuse).  Per launch i, out16[8 i ..] = {MT, BF, KS, threads,
+ * path, nblk, tiles, m_base}: the instantiation k_conv<MT, BF, KS, threads>; its K loop (path: 0 pipelined, 1 ASYNC -- the 1x1 LDS-DMA
+ * double buffer --, 2 ALLW, 3 FLAT); nblk blocks of MT x 32 output channels from channel m_base on, each over `tiles` pixel tiles.  Computed
+ * by the host code the launch itself uses, for the current device's compute units (256 without a device).  (planner / test aid) */
+int ssdn_conv_variant(const ssdn_conv_args* a, int32_t* out16);
 
 /* sizeof() of the args struct for an op type (0: ssdn_op itself); lets a binding verify its struct mirrors */
 int ssdn_struct_size(int op_type);

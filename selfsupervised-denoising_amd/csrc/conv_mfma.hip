@@ -64,6 +64,11 @@ static __host__ __device__ inline ConvGeom conv_geom(int ltw, int lth, int ltn, 
 static __host__ __device__ inline bool conv_async(const ssdn_conv_args& a, int kc) {
     if (a.ntaps != 1 || a.Ktot / kc < 2 || a.dy[0] != 0 || a.dx[0] != 0) return false;
     if (a.c0 > 0 && a.up0) return false;
+    // a workgroup-wide LDS-DMA instruction lands one 16-byte piece per lane, and a lane past the tile's last piece lands ZEROS: the tile's
+    // pieces must be whole instructions, or the surplus lanes clear the start of what lies behind the tile buffer -- the other buffer's
+    // tile, which the matrix cores are reading, or the first weight rows (64 pixels x 6 pieces on 256 lanes did: tests/test_hip_conv_walk.py)
+    const int lpx = a.ltw + a.lth + a.ltn;
+    if (((kc >> 3) << lpx) & ((lpx > 8 ? 512 : 256) - 1)) return false;
     return a.c1 == 0 || a.c0 == 0 || a.c0 % kc == 0;
 }
 
@@ -775,10 +780,13 @@ static bool conv_uses_mt1(const ssdn_conv_args* a, const ConvGeom& g) {
 
 // ALLW (-> *allw) and FLAT (returned; see k_conv) of a k_conv launch in blocks of mt x 32 output channels.  FLAT: ALLW + the 256-pixel
 // tile is made of whole images.  The two A/B knobs are read here, once, and nowhere else.
+static inline int conv_threads(const ssdn_conv_args* a) { return a->ltw + a->lth + a->ltn > 8 ? 512 : 256; }   // 257..512-pixel tiles run with 8 waves
+// the channel chunks k_conv<mt, ., kc / 16, threads> is built for (conv_launch_ks dispatches on exactly these)
+static inline bool conv_kc_built(int mt, int kc, int threads) { return kc == 16 || kc == 32 || kc == 48 || kc == 64 || (kc == 96 && mt == 1 && threads == 256); }
 static int conv_staging(const ssdn_conv_args* a, const ConvGeom& g, int mt, int* allw) {
     static const bool no_allw = ssdn_tuning_env("SSDN_CONV_NO_ALLW") != nullptr;
     static const bool no_flat = ssdn_tuning_env("SSDN_CONV_NO_FLAT") != nullptr;
-    const int ks = a->kc / 16, threads = a->ltw + a->lth + a->ltn > 8 ? 512 : 256;      // (the instantiation conv_launch_ks picks)
+    const int ks = a->kc / 16, threads = conv_threads(a);                      // (the instantiation conv_launch_ks picks)
     const int m_last = a->M - (a->Mpad - 32);                                // real channels of the last 32-channel block
     *allw = (!no_allw && conv_allw(*a, g, mt, a->kc) && !conv_async(*a, a->kc)) ? 1 : 0;
     return (*allw && !no_flat && threads == 256 && ks <= 4 && g.TW == a->W && g.TH == a->H && g.TN * g.TH * g.TW == 256 && a->N % g.TN == 0 &&
@@ -886,10 +894,26 @@ int conv_lds_bytes(const ssdn_conv_args* a) {
     return (int)conv_lds(a, r.geom, r.mt1 ? 1 : a->Mpad / 32 > 3 ? 3 : a->Mpad / 32);
 }
 
+// The k_conv launches of an op the route gives to k_conv: 32-channel blocks all in one launch (mt1), or the blocks of 96 output channels
+// (MT = 3) and then the tail as one block of MT = 2 or 1.  launch_conv walks this list; ssdn_conv_variant reports it.
+struct ConvLaunch { int mt, nblk, m_base; };
+static int conv_launches(const ssdn_conv_args* a, const ConvRoute& r, ConvLaunch out[2]) {
+    int n = 0;
+    if (r.mt1) { out[n++] = {1, a->Mpad / 32, 0}; return n; }
+    const int full = a->Mpad / 96, rem = (a->Mpad % 96) / 32;
+    if (full) out[n++] = {3, full, 0};
+    if (rem) out[n++] = {rem, 1, full * 96};
+    return n;
+}
+static int conv_lds_fits(const ssdn_conv_args* a, const ConvGeom& g, int mt) {
+    const size_t lds = conv_lds(a, g, mt);
+    return lds > 160 * 1024 ? ssdn_set_error("conv: tiling needs %zu B of LDS (> 160 KiB)", lds) : 0;
+}
+
 template <int MT, bool BF, int KS, int CONV_THREADS>
 static int conv_launch_mt(const ssdn_conv_args* a, const ConvGeom& g, ConvAux x, int nblk_y, hipStream_t s) {
-    size_t lds = conv_lds(a, g, MT);
-    if (lds > 160 * 1024) return ssdn_set_error("conv: tiling needs %zu B of LDS (> 160 KiB)", lds);
+    if (conv_lds_fits(a, g, MT)) return -1;
+    const size_t lds = conv_lds(a, g, MT);
     static bool attr_set_dev[SSDN_MAX_DEVICES_ATTR] = {};
     bool& attr_set = attr_set_dev[ssdn_current_device_slot()];   // (function attributes are per device)
     if (!attr_set) {
@@ -918,7 +942,8 @@ static int conv_launch_mt(const ssdn_conv_args* a, const ConvGeom& g, ConvAux x,
 
 template <int MT, bool BF>
 static int conv_launch_ks(const ssdn_conv_args* a, const ConvGeom& g, ConvAux x, int nblk_y, hipStream_t s) {
-    const bool wide = a->ltw + a->lth + a->ltn > 8;     // 257..512-pixel tiles run with 8 waves
+    const bool wide = conv_threads(a) == 512;
+    if (!conv_kc_built(MT, a->kc, conv_threads(a))) return ssdn_set_error("conv: unsupported kc %d", a->kc);
     switch (a->kc) {
         case 16: return wide ? conv_launch_mt<MT, BF, 1, 512>(a, g, x, nblk_y, s) : conv_launch_mt<MT, BF, 1, 256>(a, g, x, nblk_y, s);
         case 32: return wide ? conv_launch_mt<MT, BF, 2, 512>(a, g, x, nblk_y, s) : conv_launch_mt<MT, BF, 2, 256>(a, g, x, nblk_y, s);
@@ -947,6 +972,44 @@ bool conv_fuses_pool(const ssdn_conv_args* a) {
     return !conv_route(&q, &r) && route_fuses_pool(&q, r);
 }
 
+// the fused outputs and sign bytes the arguments ask for that the route's kernel cannot serve: an error, not a silent omission
+static int route_refuses(const ssdn_conv_args* a, const ConvRoute& r) {
+    if ((a->sign_out || a->mask_sign || a->upsum_mask_sign) && !route_signs(a, r)) return ssdn_set_error("conv: sign bytes requested for a launch that cannot write / read them (ssdn_conv_signs)");
+    if (a->urot.p && r.kernel != CONV_K_CDMA) return ssdn_set_error("conv: fused UNROT_FWD requested for a launch that cannot fuse it (ssdn_conv_fuses_urot)");
+    if (a->unrot.p && r.kernel != CONV_K_GDMA) return ssdn_set_error("conv: fused UNROT_BWD requested for a launch that cannot fuse it (ssdn_conv_fuses_unrot)");
+    if (a->upsum.p && !route_fuses_upsum(a, r)) return ssdn_set_error("conv: fused upsum requested for a launch that cannot fuse it (ssdn_conv_fuses_upsum)");
+    if (a->pool.p && !route_fuses_pool(a, r)) return ssdn_set_error("conv: fused max-pool requested for a launch that cannot fuse it (ssdn_conv_fuses_pool)");
+    return 0;
+}
+
+// k_conv's K loop for a launch in blocks of mt x 32 channels, as ssdn_conv_variant numbers them: what the kernel branches on, in its order
+// (x.flat and x.allw are conv_staging's answers; ASYNC is conv_async)
+static int conv_path(const ssdn_conv_args* a, const ConvGeom& g, int mt) {
+    int allw;
+    if (conv_staging(a, g, mt, &allw)) return 3;
+    return allw ? 2 : conv_async(*a, a->kc) ? 1 : 0;
+}
+
+extern "C" int ssdn_conv_variant(const ssdn_conv_args* a, int32_t* out16) {
+    if (!a || !out16) return ssdn_set_error("conv_variant: null argument");
+    ConvRoute r;
+    int rc = conv_route(a, &r);
+    if (rc) return rc;
+    if ((rc = route_refuses(a, r))) return rc;
+    if (r.kernel != CONV_K_CONV) return 0;
+    ConvLaunch l[2];
+    const int n = conv_launches(a, r, l);
+    for (int i = 0; i < n; ++i) {
+        if (!conv_kc_built(l[i].mt, a->kc, conv_threads(a))) return ssdn_set_error("conv: unsupported kc %d", a->kc);
+        if (conv_lds_fits(a, r.geom, l[i].mt)) return -1;
+        const int path = conv_path(a, r.geom, l[i].mt);
+        if ((a->pool.p || a->upsum.p) && path != 3) return ssdn_set_error("conv: fused max-pool / upsum requested for a launch that does not take the flat path");
+        const int v[8] = {l[i].mt, a->bf16 ? 1 : 0, a->kc / 16, conv_threads(a), path, l[i].nblk, r.geom.tiles_x * r.geom.tiles_y * r.geom.groups_n, l[i].m_base};
+        for (int k = 0; k < 8; ++k) out16[8 * i + k] = v[k];
+    }
+    return n;
+}
+
 extern "C" int ssdn_conv_dma_split(const ssdn_conv_args* a, int32_t* out8) {
     if (!a || !out8) return ssdn_set_error("conv_dma_split: null argument");
     ConvRoute r;
@@ -960,11 +1023,7 @@ int launch_conv(const ssdn_conv_args* a, hipStream_t s) {
     ConvRoute r;
     int rc = conv_route(a, &r);
     if (rc) return rc;
-    if ((a->sign_out || a->mask_sign || a->upsum_mask_sign) && !route_signs(a, r)) return ssdn_set_error("conv: sign bytes requested for a launch that cannot write / read them (ssdn_conv_signs)");
-    if (a->urot.p && r.kernel != CONV_K_CDMA) return ssdn_set_error("conv: fused UNROT_FWD requested for a launch that cannot fuse it (ssdn_conv_fuses_urot)");
-    if (a->unrot.p && r.kernel != CONV_K_GDMA) return ssdn_set_error("conv: fused UNROT_BWD requested for a launch that cannot fuse it (ssdn_conv_fuses_unrot)");
-    if (a->upsum.p && !route_fuses_upsum(a, r)) return ssdn_set_error("conv: fused upsum requested for a launch that cannot fuse it (ssdn_conv_fuses_upsum)");
-    if (a->pool.p && !route_fuses_pool(a, r)) return ssdn_set_error("conv: fused max-pool requested for a launch that cannot fuse it (ssdn_conv_fuses_pool)");
+    if ((rc = route_refuses(a, r))) return rc;
     switch (r.kernel) {
         case CONV_K_GDMA: return launch_gemm_dma(a, s);
         case CONV_K_THIN: return launch_conv_thin(a, nullptr, s);
@@ -988,15 +1047,17 @@ int launch_conv(const ssdn_conv_args* a, hipStream_t s) {
     }
     // output channels in blocks of 96 (MT=3); the tail uses MT = 1 or 2.  Layers with few pixel tiles are latency-bound (one
     // workgroup's pass over its tile IS the launch): they run as blocks of 32 channels (MT=1) on three times as many
-    // workgroups, each with a third of the MFMA and epilogue work.
-    int full = a->Mpad / 96, rem = (a->Mpad % 96) / 32;
+    // workgroups, each with a third of the MFMA and epilogue work.  (conv_launches)
+    ConvLaunch l[2];
+    const int nl = conv_launches(a, r, l);
     const bool bf = a->bf16 != 0;
-    if (r.mt1) rc = bf ? conv_launch_ks<1, true>(a, g, x, a->Mpad / 32, s) : conv_launch_ks<1, false>(a, g, x, a->Mpad / 32, s);
-    else {
-        if (full) rc = bf ? conv_launch_ks<3, true>(a, g, x, full, s) : conv_launch_ks<3, false>(a, g, x, full, s);
-        x.m_base = full * 96;
-        if (!rc && rem == 2) rc = bf ? conv_launch_ks<2, true>(a, g, x, 1, s) : conv_launch_ks<2, false>(a, g, x, 1, s);
-        else if (!rc && rem == 1) rc = bf ? conv_launch_ks<1, true>(a, g, x, 1, s) : conv_launch_ks<1, false>(a, g, x, 1, s);
+    for (int i = 0; i < nl && !rc; ++i) {
+        x.m_base = l[i].m_base;
+        switch (l[i].mt) {
+            case 3: rc = bf ? conv_launch_ks<3, true>(a, g, x, l[i].nblk, s) : conv_launch_ks<3, false>(a, g, x, l[i].nblk, s); break;
+            case 2: rc = bf ? conv_launch_ks<2, true>(a, g, x, l[i].nblk, s) : conv_launch_ks<2, false>(a, g, x, l[i].nblk, s); break;
+            default: rc = bf ? conv_launch_ks<1, true>(a, g, x, l[i].nblk, s) : conv_launch_ks<1, false>(a, g, x, l[i].nblk, s); break;
+        }
     }
     if (rc) return rc;
     SSDN_CHECK_HIP(hipGetLastError());

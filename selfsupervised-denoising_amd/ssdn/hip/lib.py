@@ -234,7 +234,7 @@ SYMBOLS = ["ssdn_run_ops", "ssdn_stream_order", "ssdn_conv_lds_bytes", "ssdn_wgr
            "ssdn_device_cus", "ssdn_probe_mfma", "ssdn_probe_tr16", "ssdn_struct_size", "ssdn_profile_enable",
            "ssdn_profile_read", "ssdn_profile_set_stride", "ssdn_debug_set_trace", "ssdn_debug_get_trace", "ssdn_conv_set_mode",
            "ssdn_wgrad_mergeable", "ssdn_conv_fuses_pool", "ssdn_conv_fuses_upsum", "ssdn_conv_fuses_unrot", "ssdn_conv_fuses_urot", "ssdn_conv_signs", "ssdn_chain_len",
-           "ssdn_conv_set_chain", "ssdn_wgrad_mega_ok", "ssdn_wgrad_variant", "ssdn_conv_dma_split", "ssdn_conv16_eligible", "ssdn_conv_set_conv16",
+           "ssdn_conv_set_chain", "ssdn_wgrad_mega_ok", "ssdn_wgrad_variant", "ssdn_conv_dma_split", "ssdn_conv_variant", "ssdn_conv16_eligible", "ssdn_conv_set_conv16",
            "ssdn_plan_load", "ssdn_plan_destroy", "ssdn_plan_arena_bytes", "ssdn_plan_meta", "ssdn_plan_bind", "ssdn_plan_tensor", "ssdn_plan_run",
            "ssdn_plan_set_lr", "ssdn_net_forward", "ssdn_train_step"]
 PLAN_PHASES = dict(repack=0, forward=1, backward=2, optimiser=3)
@@ -347,6 +347,9 @@ def load() -> C.CDLL:
     if hasattr(lib, "ssdn_conv_dma_split"):      # (older builds loaded through SSDN_HIP_LIB do not answer the query)
         lib.ssdn_conv_dma_split.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         lib.ssdn_conv_dma_split.restype = C.c_int
+    if hasattr(lib, "ssdn_conv_variant"):
+        lib.ssdn_conv_variant.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        lib.ssdn_conv_variant.restype = C.c_int
     lib.ssdn_struct_size.argtypes = [C.c_int]
     lib.ssdn_struct_size.restype = C.c_int
     lib.ssdn_plan_load.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_void_p)]

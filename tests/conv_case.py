@@ -14,7 +14,10 @@ a fixed chain of fp32 operations and one round-to-nearest-even conversion, which
 
 Used by tests/test_hip_conv16.py (k_conv16 against k_conv), tests/test_hip_cdma_walk.py / tests/test_cdma_walk_cpu.py (k_cdma's tile
 walk), tests/test_hip_conv_route.py (one launch per kernel of SSDN_OP_CONV) and tests/test_hip_gdma_walk.py / tests/test_gdma_walk_cpu.py
-(k_gdma's tile walk and epilogues)."""
+(k_gdma's tile walk and epilogues), and by tests/test_hip_conv_walk.py / tests/test_conv_walk_cpu.py (k_conv per launch), which need the
+rest: tile=(ltw, lth, ltn, kc) in place of the planner's tiling; pool=True (pool_shifted 0 / 1): the fused max-pool output, a channel window
+of a wide tensor of its own; act=True under ints=True on a 3x3 layer (the fused pool needs the activation) and ints=True with dst32 -- both
+follow the exact integer sum with the kernel's fixed fp32 chain (ints_expected)."""
 import ctypes as C
 
 import torch
@@ -23,7 +26,9 @@ SLOPE = 0.1
 INT_NNZ = 32        # +-1 entries per weight row of the integer operands (see Case._int_operands for the bound this gives)
 INT_IN, INT_BIAS, INT_ADD = 2, 4, 8      # |input|, |bias|, |addend| of the integer operands
 INT_LIMIT = 256     # integers up to here are exact in bf16 (8 significant bits) and in fp16 (11)
-NEXT_GUARD = 256    # fp32 elements in front of and behind the second layer's output that must stay NaN
+NEXT_GUARD = 256    # fp32 elements in front of and behind the second layer's output (and a dst32 output) that must stay NaN
+VARIANT_FIELDS = ("MT", "BF", "KS", "threads", "path", "nblk", "tiles", "m_base")      # ssdn_conv_variant, per launch
+PATHS = ("pipe", "async", "allw", "flat")                                              # ... its `path`
 
 
 def _dev():
@@ -75,11 +80,12 @@ class Case:
 
     def __init__(self, role, N, c0, c1, up0, M, taps, H=16, W=16, mask=False, add=False, upsum_c=0, bias=None, seed=0, dst32=False,
                  edge=False, cm=False, ints=False, sign_out=False, mask_sign=False, upsum_mask_sign=False, urot=False, urot_smask=False,
-                 kreal=0, device=True, unrot=False, unrot_smask=False, next=None):
+                 kreal=0, device=True, unrot=False, unrot_smask=False, next=None, tile=None, pool=False, pool_shifted=0, act=None):
         from ssdn.hip.graph import choose_conv_tile
         L, lib = _lib()
         self.role, self.N, self.H, self.W, self.c0, self.c1, self.up0, self.M, self.upsum_c = role, N, H, W, c0, c1, up0, M, upsum_c
         self.ints, self.device, self.urot, self.unrot, self.next = ints, device, urot, unrot, next
+        self.pool, self.pool_shifted = pool, pool_shifted
         bf = role == "dgrad"
         self.dt = torch.bfloat16 if bf else torch.float16
         self.taps = [(-dy, -dx) for dy, dx in taps] if bf else list(taps)      # the data gradient walks the mirrored window
@@ -166,6 +172,9 @@ class Case:
         # (the integer operands: no LeakyReLU -- but for a 1x1 layer, whose expectation follows the fp32 chain behind the sum; in front of a
         # second layer the tile must hold integers)
         a.act = int(not bf and (not ints or (len(self.taps) == 1 and next is None)))
+        if act is not None:       # (integer operands on a 3x3 layer with the activation: ints_expected follows the fp32 chain there too)
+            assert not bf and not mask and not add
+            a.act = int(act)
         if mask:
             _, a.mask = view(self.mask, window=not mask_sign)
             if mask_sign:
@@ -177,7 +186,9 @@ class Case:
         if dst32 and not device:
             a.dst32 = 0x1000
         elif dst32:
-            self.outs["dst32"] = torch.empty(N, M, H, W, device=_dev())
+            # (NEXT_GUARD elements in front of and behind the output: launch() leaves them in dst32_guards, still NaN if nothing stored there)
+            self.dst32_buf = torch.empty(N * M * H * W + 2 * NEXT_GUARD, device=_dev())
+            self.outs["dst32"] = self.dst32_buf[NEXT_GUARD:NEXT_GUARD + N * M * H * W].view(N, M, H, W)
             a.dst32 = self.outs["dst32"].data_ptr()
         elif urot:
             self.outs["urot"], a.urot = view(torch.zeros(N // 4, H, W, 4 * M, dtype=self.dt))
@@ -199,6 +210,9 @@ class Case:
                 _, a.unrot_mask = view(self.unrot_mask)
         if sign_out:
             a.sign_out = self._bytes("sign_out", (N, H, W, M // 8))
+        if pool:
+            self.outs["pool"], a.pool = view(torch.zeros(N, H // 2, W // 2, M, dtype=self.dt))
+            a.pool_shifted = pool_shifted
         if upsum_c:
             self.outs["upsum"], a.upsum = view(torch.zeros(N, H // 2, W // 2, upsum_c, dtype=self.dt))
             _, a.upsum_mask = view(self.umask, window=not upsum_mask_sign)
@@ -206,7 +220,7 @@ class Case:
                 a.upsum_mask_sign = raw(pack_signs(self.umask.float()))
             a.upsum_c = upsum_c
         cus = lib.ssdn_device_cus()
-        a.ltw, a.lth, a.ltn, a.kc = choose_conv_tile(N, H, W, self.taps, self.Ktot, self.Mpad, out16=not dst32, cus=cus if cus > 0 else 256)
+        a.ltw, a.lth, a.ltn, a.kc = tile or choose_conv_tile(N, H, W, self.taps, self.Ktot, self.Mpad, out16=not dst32, cus=cus if cus > 0 else 256)
         a.bf16, a.kreal = int(bf), kreal or self.Ktot
         if cm:
             # the chunk-major copy SSDN_OP_WPACK writes next to the shadow (ssdn_conv_args.wc), by the host model tests/test_hip_optimiser.py
@@ -270,10 +284,10 @@ class Case:
         s1 = _randint(gen, (N, H, W, self.c1), INT_IN) if self.c1 else None
         ntaps = len(self.taps)
         P = ntaps * Ktot
-        assert INT_NNZ <= P
+        nnz = min(INT_NNZ, P)     # (a 1x1 layer of 16 input channels has only 16 positions: every one is hit, the bounds only shrink)
         perm = torch.randperm(P, generator=gen)
-        pos = perm[(torch.arange(M)[:, None] * INT_NNZ + torch.arange(INT_NNZ)[None, :]) % P]        # [M][INT_NNZ] -> tap * Ktot + k
-        sign = torch.randint(0, 2, (M, INT_NNZ), generator=gen).float() * 2 - 1
+        pos = perm[(torch.arange(M)[:, None] * nnz + torch.arange(nnz)[None, :]) % P]                # [M][nnz] -> tap * Ktot + k
+        sign = torch.randint(0, 2, (M, nnz), generator=gen).float() * 2 - 1
         w = torch.zeros(ntaps, self.Mpad, Ktot)
         w[pos // Ktot, torch.arange(M)[:, None].expand_as(pos), pos % Ktot] = sign
         self.w_hits = torch.bincount(pos.reshape(-1), minlength=P)                                  # rows per (tap, channel) position
@@ -288,6 +302,15 @@ class Case:
     def eligible(self):
         L, lib = _lib()
         return lib.ssdn_conv16_eligible(C.byref(self.a))
+
+    def variant(self):
+        """ssdn_conv_variant -> the k_conv launches the op makes: a list of {MT, BF, KS, threads, path, nblk, tiles, m_base} (empty: another
+        kernel serves it)"""
+        L, lib = _lib()
+        out = (C.c_int32 * 16)()
+        rc = lib.ssdn_conv_variant(C.byref(self.a), out)
+        assert rc >= 0, lib.ssdn_last_error()
+        return [dict(zip(VARIANT_FIELDS, out[8 * i:8 * i + 8])) for i in range(rc)]
 
     def split(self):
         """ssdn_conv_dma_split -> (k_cdma serves the launch, {tiles_x, tiles_y, segs, tps, nitems, grid, xcd_map, mt_blocks})"""
@@ -306,9 +329,13 @@ class Case:
             t.fill_(0xA5)
         if self.next is not None:
             self.next_buf.fill_(float("nan"))
+        if "dst32" in self.outs:
+            self.dst32_buf.fill_(float("nan"))
         OpList([("conv", self.a)] + ([("conv", self.a4)] if self.next is not None else [])).run(current_stream())
         torch.cuda.synchronize()
         got = {k: t.detach().cpu().clone() for k, t in self.outs.items()}
+        if "dst32" in self.outs:
+            self.dst32_guards = torch.cat([self.dst32_buf[:NEXT_GUARD], self.dst32_buf[-NEXT_GUARD:]]).cpu()
         got.update({k: t.detach().cpu().clone() for k, t in self.bytes_out.items()})
         if self.next is not None:
             got["next32"] = self.next_buf.detach().cpu().clone()       # (with its guards)
@@ -388,6 +415,8 @@ class Case:
         slope = torch.tensor(SLOPE, dtype=torch.float32, device=pre.device)
         one = torch.ones((), dtype=torch.float32, device=pre.device)
         x = pre.float() + 0.0
+        if self.a.dst32:      # k_conv's fp32 NCHW output: the integer sum (+ bias) in fp32, then v > 0 ? v : 0.1f v; nothing else is applied
+            return {"dst32": (torch.where(x > 0, x, x * slope) if self.a.act else x).permute(0, 3, 1, 2).contiguous()}
         if self.a.act:
             x = torch.maximum(x, x * slope)
         x = x.to(self.dt)
@@ -413,6 +442,31 @@ class Case:
             out["next32"] = buf
         return out
 
+    def _ints_act(self, dev=None):
+        """a 3x3 layer's integer expectation with the activation and / or the fp32 output.  The sum (+ bias) v is an exact integer in any
+        order; k_conv follows it with v > 0 ? v : 0.1f v in fp32 (common.h::lrelu) and ONE round-to-nearest-even conversion to fp16
+        (dst32: none), repeated here in torch float32.  The fused max-pool is exact on the rounded values: the whole wide tensor."""
+        assert self.add is None and self.mask is None and not self.upsum_c and not self.urot
+        self.ref64(dev)
+        pre = self.pre
+        assert bool((pre == pre.round()).all()) and float(pre.abs().max()) <= INT_LIMIT, "integer reference: |v| max %g" % float(pre.abs().max())
+        slope = torch.tensor(SLOPE, dtype=torch.float32, device=pre.device)
+        x = pre.float() + 0.0
+        if self.a.act:
+            x = torch.where(x > 0, x, x * slope)
+        if self.a.dst32:
+            return {"dst32": x.permute(0, 3, 1, 2).contiguous()}
+        x = x.to(self.dt)
+
+        def wide(t):
+            o = torch.full(t.shape[:-1] + (t.shape[-1] + 16,), float("nan"), dtype=self.dt, device=t.device)
+            o[..., 8:8 + t.shape[-1]] = t
+            return o
+        out = {"dst": wide(x)}
+        if self.pool:
+            out["pool"] = wide(pool_of(x.float().cpu(), self.pool_shifted).to(self.dt).to(x.device))
+        return out
+
     def ints_expected(self, dev=None):
         """the integer operands' expected outputs {name: the whole wide tensor, NaN where the launch stores nothing}, after asserting the
         condition that makes them exact in any accumulation order and in the 16-bit output type: every value, fused 2x2 up-sums included,
@@ -420,6 +474,8 @@ class Case:
         assert self.ints
         if len(self.taps) == 1:
             return self._ints_chain(dev)
+        if self.a.act or self.a.dst32:
+            return self._ints_act(dev)
         ref, up, _ = self.ref64(dev)
         for r in (ref, up):
             if r is not None:
@@ -437,6 +493,13 @@ class Case:
         if uc:
             out["upsum"] = wide(up)
         return out
+
+
+def pool_of(x, shifted):
+    """SSDN_OP_POOL_FWD of include/ssdn_hip.h on x [N,H,W,C] (oracle/interp.py::Interp._windows(...).max): 2x2 windows; shifted: of the
+    image moved one row down, a zero row on top"""
+    from interp import Interp
+    return Interp._windows(None, x, shifted).max(3).values
 
 
 def _bits(t):
@@ -500,6 +563,27 @@ def _check_ref(case, got, sparse=False, dev=None):
         assert bool(torch.isnan(got["upsum"][..., :8].float()).all()) and bool(torch.isnan(got["upsum"][..., 8 + uc:].float()).all())
 
 
+def _check_dst32(case, got, dev=None):
+    """fp32 NCHW output of fp16 operands: the forward bound of _check_ref; the guards in front of and behind the buffer are still NaN"""
+    ref = case.ref64(dev)[0].permute(0, 3, 1, 2)
+    tol = 2e-3 * ref.abs() + 2e-3 * float(ref.abs().max()) * 1e-2 + 1e-9
+    g = got["dst32"].to(ref.device).double()
+    assert bool(torch.isfinite(g).all())
+    err = (g - ref).abs()
+    assert bool((err <= tol).all()), "dst32: %d elements beyond the bound, max err %.3e" % (int((err > tol).sum()), float(err.max()))
+    assert bool(torch.isnan(case.dst32_guards).all()), "stored outside the fp32 output"
+
+
+def check_pool(case, got):
+    """the fused max-pool output is exactly SSDN_OP_POOL_FWD of what the launch itself stored (the max is exact on the rounded values),
+    as tests/test_hip_ops.py::test_every_op_teacher_forced has it; the guard channels of its wide tensor are still NaN"""
+    M = case.M
+    want = pool_of(got["dst"][..., 8:8 + M].float(), case.pool_shifted)
+    gp = got["pool"]
+    assert torch.equal(gp[..., 8:8 + M].float(), want), "fused max-pool differs from pool(dst) in %d elements" % int((gp[..., 8:8 + M].float() != want).sum())
+    assert bool(torch.isnan(gp[..., :8].float()).all()) and bool(torch.isnan(gp[..., 8 + M:].float()).all())
+
+
 def _check_next32(case, got, dev=None):
     """the second layer's fp32 NCHW output against float64 on the first layer's own stored 16-bit output: the forward bound of _check_ref
     (as tests/test_hip_conv_route.py::_check_dst32); the guards in front of and behind it are still NaN"""
@@ -520,6 +604,8 @@ def check_ints(case, got, dev=None):
     """bit equality of every 16-bit output -- the whole wide tensor: the window holds the float64 reference cast to the output type, every
     other element (guard channels, the channels that only exist as up-sums, the rows a fused UNROT_FWD leaves empty) is still the NaN it was"""
     want = case.ints_expected(dev)
+    if "dst32" in want:
+        assert bool(torch.isnan(case.dst32_guards).all()), "stored outside the fp32 output"
     for k, w in want.items():
         g = got[k].to(w.device)
         diff = _bits(g) != _bits(w)

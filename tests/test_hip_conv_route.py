@@ -5,9 +5,8 @@ tests/test_hip_ops.py::test_every_op_teacher_forced (conv_case._check_ref).  Onl
 import ctypes as C
 
 import pytest
-import torch
 
-from conv_case import Case, _check_ref
+from conv_case import Case, _check_dst32, _check_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -90,16 +89,6 @@ def predicted(case, mode):
     if rem:
         n["conv_mt2" if rem == 2 else "conv_mt1"] += 1
     return "k_conv", n
-
-
-def _check_dst32(case, got):
-    """fp32 NCHW output of fp16 operands: the forward bound of conv_case._check_ref"""
-    ref = case.ref64()[0].permute(0, 3, 1, 2)
-    tol = 2e-3 * ref.abs() + 2e-3 * float(ref.abs().max()) * 1e-2 + 1e-9
-    g = got["dst32"].double()
-    assert bool(torch.isfinite(g).all())
-    err = (g - ref).abs()
-    assert bool((err <= tol).all()), "dst32: %d elements beyond the bound, max err %.3e" % (int((err > tol).sum()), float(err.max()))
 
 
 @pytest.mark.parametrize("name", list(CASES))
