@@ -80,7 +80,12 @@ enum ssdn_op_type {
     SSDN_OP_NOISE_EST = 31,     /* a blind per-image noise-level estimate (gauss sigma, poisson lambda) from the packed uint8 images SSDN_OP_IMAGE_IN reads (no planned list holds it) */
     SSDN_OP_TILE_IN = 32,       /* one uint8 image of any size -> a batch of its fixed-size overlapping tiles: / 255, transposed, reflected beyond the image (no planned list holds it) */
     SSDN_OP_TILE_OUT = 33,      /* the fp32 tiles of one image -> that image, blended across the overlaps: bytes or upright fp32 planes (no planned list holds it) */
-    SSDN_OP_POOL_PATCH = 34     /* a minibatch of training patches cut out of a device-resident pool of uint8 images: crop, dihedral transform, / 255 (+ Noise2Void) (no planned list holds it) */
+    SSDN_OP_POOL_PATCH = 34,    /* a minibatch of training patches cut out of a device-resident pool of uint8 images: crop, dihedral transform, / 255 (+ Noise2Void) (no planned list holds it) */
+    SSDN_OP_IMAGE_IN16 = 35,    /* SSDN_OP_IMAGE_IN for packed uint16 images: min(s, white) / white (no planned list holds it) */
+    SSDN_OP_IMAGE_OUT16 = 36,   /* SSDN_OP_IMAGE_OUT writing uint16: clipped, * white, rounded to nearest even (no planned list holds it) */
+    SSDN_OP_TILE_IN16 = 37,     /* SSDN_OP_TILE_IN from one uint16 image (no planned list holds it) */
+    SSDN_OP_TILE_OUT16 = 38,    /* SSDN_OP_TILE_OUT's blend, quantised to uint16 [h][w][C] (no planned list holds it) */
+    SSDN_OP_POOL_PATCH16 = 39   /* SSDN_OP_POOL_PATCH over a planar uint16 pool (no planned list holds it) */
 };
 
 /* One record of the op list.  `args` points at the matching ssdn_*_args struct (host memory).
@@ -851,6 +856,93 @@ typedef struct ssdn_pool_patch_args {
     int32_t n2v_box, n2v_radius;
     uint64_t seed, offset;
 } ssdn_pool_patch_args;
+
+/* ---- SSDN_OP_IMAGE_IN16 / IMAGE_OUT16 / TILE_IN16 / TILE_OUT16 / POOL_PATCH16 -------------------------
+ * The five byte ops above for 16-bit images: microscopy, astronomy, radiography, raw sensor data -- 12, 14 or 16 significant bits in a
+ * 16-bit container.  The samples cross the bus as integers, 2 bytes each; they become the engine's fp32 on the device and come back
+ * quantised.  tests/image16_ref.py is this text in numpy.  One sample model for all five:
+ *   sample: a uint16 in host byte order.  white: int32 in [1, 65535], the sample value that means 1.0 (65535 full range, 4095 a 12-bit
+ *     camera file: scaled by 65535 such an image would be nearly black and a noise parameter in units of white / 255 would mean nothing).
+ *   in:   value = (float)min(s, white) / (float)white      one true fp32 division, as the byte ops' / 255.f; samples above white are 1.0
+ *   out:  q16(v) = (uint16) rint(fl(min(max(v, 0), 1) * (float)white))      one fp32 product rounded on its own, then round to nearest,
+ *     ties to even; q16(NaN) = 0, q16(-0.0) = 0.
+ *   q16 rounds where SSDN_OP_IMAGE_OUT's q truncates: q follows the reference's tensor2image, q16 has no reference to follow, and
+ *   truncation does not survive the round trip (white = 1000: 5 of 1001 samples come back one too low).  With rounding q16(in(s)) = s for
+ *   every s <= white and every white: |fl(fl(s / white) white) - s| <= ~2 * 2^-24 * 65535 < 0.5.
+ *   With white = 255 and samples that are widened bytes the "in" direction is the byte ops' value bit for bit.
+ * Everything else is the sibling's definition with "byte" read as "sample": src_count, dst_count, offs[b] and the pool's offsets[i] count
+ * SAMPLES, so every access is 2-byte aligned by construction.  The guard of the image ops is 0 <= offs[b] < count and
+ * idx < count - offs[b]; a read outside yields 0, a write outside is dropped.
+ *   IMAGE_IN16:   dst[b,c,i,j] = in(src_b[(r(j, e2) e1 + r(i, e1)) C + c])
+ *   IMAGE_OUT16:  dst_b[(y e1 + x) C + c] = q16(x[b,c,x,y]) for x < e1, y < e2; no sample outside an image's h_b w_b C samples is written
+ *   TILE_IN16:    dst[b,c,i,j] = in(src[(r(oy + j, h) w + r(ox + i, w)) C + c])
+ *   TILE_OUT16:   dst[(y w + x) C + c] = q16(blend), SSDN_OP_TILE_OUT's blend: the same t, the same order, every operation rounded on its
+ *                 own.  There is no mode: the fp32 std map goes through SSDN_OP_TILE_OUT mode 1.
+ *   POOL_PATCH16: image i is planar uint16 [C, rows_i, cols_i] at sample offsets[i]; value = in(sample).  The Philox draws, crop,
+ *                 transform, Noise2Void selection, coords, param_out and origin_out are SSDN_OP_POOL_PATCH's: for equal (seed, offset,
+ *                 sizes, index) the two ops give equal origin_out and coords.
+ * Kernels (csrc/image_io16.hip, tile_io16.hip, patch_pool16.hip): the siblings' shapes -- one workgroup per
+ * 32 x 64 patch with the transposition through an LDS tile of odd pitch holding fp32 or unsigned words (image and tile ops), one thread
+ * per output pixel (pool op).
+ * Argument errors are raised before any device call, the siblings' texts under the prefixes "image_in16:", "image_out16:", "tile_in16:",
+ * "tile_out16:", "pool_patch16:", and "white must lie in [1, 65535]".  Adding these ops changed no existing struct: the ABI version
+ * stays. */
+typedef struct ssdn_image_in16_args {
+    const uint16_t* src;  /* packed images, device */
+    int64_t src_count;    /* samples */
+    const int64_t* offs;  /* device [B], in samples */
+    const int32_t* ext;   /* device [B][2] = (w_b, h_b) */
+    int32_t B, C, H, W;
+    int32_t white;
+    float* dst;           /* out [B,C,H,W]: every element is written */
+} ssdn_image_in16_args;
+
+typedef struct ssdn_image_out16_args {
+    const float* x;       /* [B,C,H,W] */
+    const int32_t* ext;   /* device [B][2] = (w_b, h_b) */
+    const int64_t* offs;  /* device [B], in samples */
+    uint16_t* dst;        /* packed images out, device */
+    int64_t dst_count;    /* samples */
+    int32_t B, C, H, W;
+    int32_t white;
+} ssdn_image_out16_args;
+
+typedef struct ssdn_tile_in16_args {
+    const uint16_t* src;  /* the image, device */
+    int64_t src_count;    /* samples, >= w h C */
+    int32_t w, h, C;
+    int32_t T, O, Kx, Ky;
+    int32_t k0, B;        /* the tiles k0 .. k0 + B - 1 */
+    int32_t white;
+    float* dst;           /* out [B,C,T,T]: every element is written */
+} ssdn_tile_in16_args;
+
+typedef struct ssdn_tile_out16_args {
+    const float* store;   /* [Kx Ky, C, T, T] */
+    int32_t w, h, C;
+    int32_t T, O, Kx, Ky;
+    int32_t white;
+    uint16_t* dst;        /* out uint16 [h][w][C], device */
+    int64_t dst_count;    /* samples, >= w h C */
+} ssdn_tile_out16_args;
+
+typedef struct ssdn_pool_patch16_args {
+    const uint16_t* pool;     /* the packed images, device */
+    const int64_t* offsets;   /* [N] sample offset of every image */
+    const int32_t* sizes;     /* [N][2] (rows, cols) */
+    const float* params;      /* [N] per-image noise parameter, may be NULL */
+    const int32_t* index;     /* [B] the image of every sample */
+    float* noisy32;           /* out [B,C,P,P] */
+    float* ref32;             /* out [B,C,P,P], may be NULL: the unmanipulated patch */
+    int64_t* coords;          /* out [B, (P / n2v_box)^2, 2], n2v_box > 0 only */
+    float* param_out;         /* out [B C], may be NULL */
+    int32_t* origin_out;      /* out [B][3] (x0, y0, d), may be NULL */
+    int32_t N, B, C, P;
+    int32_t augment;          /* 0: d = 0 */
+    int32_t n2v_box, n2v_radius;
+    int32_t white;
+    uint64_t seed, offset;
+} ssdn_pool_patch16_args;
 
 /* ---- SSDN_OP_INPUT_GRAD --------------------------------------------------------------------
  * replaces: the data gradient autograd propagates into the network input through the first conv (noise_network.py:69-71) and the

@@ -118,6 +118,11 @@ int ssdn_struct_size(int op_type) {
         case SSDN_OP_TILE_IN: return (int)sizeof(ssdn_tile_in_args);
         case SSDN_OP_TILE_OUT: return (int)sizeof(ssdn_tile_out_args);
         case SSDN_OP_POOL_PATCH: return (int)sizeof(ssdn_pool_patch_args);
+        case SSDN_OP_IMAGE_IN16: return (int)sizeof(ssdn_image_in16_args);
+        case SSDN_OP_IMAGE_OUT16: return (int)sizeof(ssdn_image_out16_args);
+        case SSDN_OP_TILE_IN16: return (int)sizeof(ssdn_tile_in16_args);
+        case SSDN_OP_TILE_OUT16: return (int)sizeof(ssdn_tile_out16_args);
+        case SSDN_OP_POOL_PATCH16: return (int)sizeof(ssdn_pool_patch16_args);
         default: return -1;
     }
 }
@@ -423,6 +428,11 @@ int ssdn_run_ops(const ssdn_op* ops, int n, void* stream) {
             case SSDN_OP_TILE_IN: rc = launch_tile_in((const ssdn_tile_in_args*)p, s); break;
             case SSDN_OP_TILE_OUT: rc = launch_tile_out((const ssdn_tile_out_args*)p, s); break;
             case SSDN_OP_POOL_PATCH: rc = launch_pool_patch((const ssdn_pool_patch_args*)p, s); break;
+            case SSDN_OP_IMAGE_IN16: rc = launch_image_in16((const ssdn_image_in16_args*)p, s); break;
+            case SSDN_OP_IMAGE_OUT16: rc = launch_image_out16((const ssdn_image_out16_args*)p, s); break;
+            case SSDN_OP_TILE_IN16: rc = launch_tile_in16((const ssdn_tile_in16_args*)p, s); break;
+            case SSDN_OP_TILE_OUT16: rc = launch_tile_out16((const ssdn_tile_out16_args*)p, s); break;
+            case SSDN_OP_POOL_PATCH16: rc = launch_pool_patch16((const ssdn_pool_patch16_args*)p, s); break;
             case SSDN_OP_ZERO: {
                 const ssdn_zero_args* z = (const ssdn_zero_args*)p;
                 if (z->bytes & 15) return ssdn_set_error("op %d: zero size must be a multiple of 16", i);

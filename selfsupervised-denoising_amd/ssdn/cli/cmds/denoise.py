@@ -1,10 +1,11 @@
 """`ssdn denoise --model M --input I --output O [--noise_param P|auto] [--batch_size B] [--bucket N] [--uniform] [--std] [--recursive]
-[--tile T] [--overlap O]`:
+[--tile T] [--overlap O] [--white W]`:
 denoise already noisy images with a trained model (the reference has no such command: its evaluator takes clean datasets and adds
 the noise itself).  I: an image file or a folder of images (file discovery and channel conversion of datasets/folder.py); writes
 O/<relative stem>.png, with --std O/<relative stem>_std.npy (float32 [C,h,w] posterior std dev, ssdn models only), and O/denoise.csv
 with one row per image (with --noise_param auto also the noise parameter estimated for it, with --tile also the number of tiles it was
-cut into).  PNG decode and encode stay on the host
+cut into).  A 16-bit grey file (ssdn.utils.load_image) comes back as a 16-bit grey PNG; --white W is the sample value that means 1.0 in such
+files (default 65535; 4095 for a 12-bit camera file).  PNG decode and encode stay on the host
 with PIL; everything between is `Denoiser.denoise`."""
 import os
 from typing import Dict, List, Tuple
@@ -52,13 +53,17 @@ class DenoiseCommand(Command):
         p.add_argument("--overlap", type=int, default=None,
                        help="The overlap of neighbouring tiles (a multiple of 32, at most half of --tile; default a quarter of it).")
 
+        p.add_argument("--white", type=int, default=None,
+                       help="The sample value that means 1.0 in 16-bit input files (an integer in [1, 65535], default 65535; 4095 for a "
+                            "12-bit camera file).  Only with 16-bit inputs, which are written back as 16-bit grey PNGs.")
+
     def execute(self, args: Dict):
         import numpy as np
         import torch
         from PIL import Image
         from ssdn.denoiser import Denoiser
         from ssdn.params import ConfigValue
-        from ssdn.utils.data import set_color_channels
+        from ssdn.utils.data import load_image, save_image16
         sd = torch.load(args["model"], map_location="cpu", weights_only=False)
         denoiser = Denoiser.from_state_dict(sd["denoiser"] if "denoiser" in sd else sd)
         channels = denoiser.cfg[ConfigValue.IMAGE_CHANNELS]
@@ -68,11 +73,9 @@ class DenoiseCommand(Command):
         base, files = find_images(args["input"], bool(args.get("recursive")))
         images = []
         for path in files:
-            with open(path, "rb") as f:
-                img = Image.open(f)
-                img.load()
-            images.append(np.asarray(set_color_channels(img, channels), dtype=np.uint8))
-        res = denoiser.denoise(images, **opts)
+            a = load_image(path, channels)
+            images.append(a[:, :, 0] if a.shape[2] == 1 else a)
+        res = denoiser.denoise(images, white=args.get("white"), **opts)
         out_dir = args["output"]
         os.makedirs(out_dir, exist_ok=True)
         with open(os.path.join(out_dir, "denoise.csv"), "w") as csv:
@@ -81,7 +84,10 @@ class DenoiseCommand(Command):
             for k, path in enumerate(files):
                 stem = os.path.splitext(os.path.relpath(path, base))[0]
                 os.makedirs(os.path.dirname(os.path.join(out_dir, stem)) or out_dir, exist_ok=True)
-                Image.fromarray(res["out"][k].numpy()).save(os.path.join(out_dir, stem + ".png"))
+                if res["out"][k].dtype == torch.uint16:
+                    save_image16(res["out"][k], os.path.join(out_dir, stem + ".png"))
+                else:
+                    Image.fromarray(res["out"][k].numpy()).save(os.path.join(out_dir, stem + ".png"))
                 if "std" in res:
                     np.save(os.path.join(out_dir, stem + "_std.npy"), res["std"][k].numpy().astype(np.float32))
                 h, w = images[k].shape[:2]

@@ -3,8 +3,9 @@
 `NoisyDataset` and `DevicePatchStream` start from a clean image and synthesise the corruption; the three pipelines that never read a clean
 image in their loss (ssdn, ssdn_u_only, n2v) can train on a folder of noisy images alone.  `ImagePool` decodes every training image ONCE,
 packs the bytes back to back and keeps them on the device; `DevicePoolStream` cuts every minibatch out of that pool with ONE launch
-(SSDN_OP_POOL_PATCH of libssdn_hip.so: random crop, optional dihedral transform, / 255, the Noise2Void manipulation) that writes straight
-into the denoiser's input buffer.  No DataLoader, no workers, no upload per step beyond the B image numbers.
+(SSDN_OP_POOL_PATCH of libssdn_hip.so: random crop, optional dihedral transform, / 255, the Noise2Void manipulation; SSDN_OP_POOL_PATCH16
+with min(sample, white) / white for a 16-bit pool) that writes straight into the denoiser's input buffer.  No DataLoader, no workers, no
+upload per step beyond the B image numbers.
 
 Yields `[inp, ref, metadata]` in the contract of `DevicePatchStream` (same keys, shapes and dtypes) except that `Metadata.CLEAN` is absent:
 there is no clean image.  An image smaller than the patch is extended by reflection to the right and downwards only (the host `RandomCrop`
@@ -28,44 +29,111 @@ class ImagePool:
     `dataset[i][0]`, converted as `CleanPatches.__getitem__` converts (x 255, round, clamp, uint8), packed without padding and uploaded:
     `pool` uint8 [total], `offsets` int64 [N], `sizes` int32 [N, 2] = (rows, cols) of the dataset's own planar [C, rows, cols] tensor, and
     optionally `params` fp32 [N], the per-image noise parameter.  The host keeps `files`, the length and copies of offsets and sizes.
-    In a multi-GPU job every rank holds the whole pool."""
+    In a multi-GPU job every rank holds the whole pool.
+    A folder whose files are all 16-bit grey (their PIL modes, read from the headers) becomes a 16-bit pool: `bits` = 16, `pool` uint16 in
+    the same planar layout, read through `ssdn.utils.load_image` (the dataset's own route clips at 255), `offsets` in SAMPLES, `nbytes` and
+    the cap at 2 bytes per sample, `white` the sample value that means 1.0 (None = 65535).  Files of both depths are refused; HDF5 datasets
+    are 8-bit; `white` with an 8-bit pool is refused."""
 
-    def __init__(self, dataset, device, max_bytes: int = DEFAULT_POOL_BYTES):
+    def __init__(self, dataset, device, max_bytes: int = DEFAULT_POOL_BYTES, white: Optional[int] = None):
         if getattr(dataset, "transform", None) is not None:
             raise ValueError("ImagePool: the dataset must be untransformed (the pool holds whole images; the crop is the stream's)")
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
         n = len(dataset)
         if n < 1:
             raise ValueError("ImagePool: the dataset is empty")
-        self.files: Optional[List[str]] = list(dataset.files) if hasattr(dataset, "files") else None
-        self.max_bytes = int(max_bytes)
-        if hasattr(dataset, "image_size"):          # the headers alone tell whether the pool fits: nothing is decoded for a folder that does not
-            total = sum(int(torch.prod(dataset.image_size(i, ignore_transform=True))) for i in range(n))
-            self._check_cap(total, n)
+        self._start(device, max_bytes, list(dataset.files) if hasattr(dataset, "files") else None)
+        bits = 8
+        if self.files is not None:                  # the headers alone tell the depth and whether the pool fits: nothing is decoded before
+            bits, total = self._read_headers(int(getattr(dataset, "channels", 0)))
+            if hasattr(dataset, "image_size"):
+                self._check_cap(total * (bits // 8), n)
+        elif hasattr(dataset, "image_size"):
+            self._check_cap(sum(int(torch.prod(dataset.image_size(i, ignore_transform=True))) for i in range(n)), n)
+        if bits == 16:
+            from ssdn.utils.data import load_image
+            swap = getattr(dataset, "output_format", "CHW") is not None      # the dataset's own relabelling (datasets/folder.py)
+
+            def read(i):
+                t = torch.from_numpy(load_image(self.files[i], dataset.channels))              # uint16 [h, w, 1]
+                return (t.permute(2, 1, 0) if swap else t.permute(2, 0, 1)).contiguous()
+        else:
+            def read(i):
+                img = dataset[i][0]
+                if img.dim() != 3:
+                    raise ValueError("ImagePool: image %d is not a [C, rows, cols] tensor" % i)
+                return (img * 255.0).round().clamp_(0, 255).to(torch.uint8).contiguous()
+        self._fill(n, read, bits, white)
+
+    @classmethod
+    def from_images(cls, images, device, max_bytes: int = DEFAULT_POOL_BYTES, white: Optional[int] = None) -> "ImagePool":
+        """A pool of upright arrays or tensors [h, w] or [h, w, C], all uint8 or all uint16 -- the route for 16-bit RGB, which no PIL file
+        delivers.  Image i is stored as the datasets would hand it out: planar [C, w, h] (rows run along the picture's x)."""
+        import numpy as np
+        ts = []
+        for k, im in enumerate(images):
+            t = torch.from_numpy(np.ascontiguousarray(im)) if isinstance(im, np.ndarray) else im
+            if not torch.is_tensor(t) or t.dtype not in (torch.uint8, torch.uint16) or t.dim() not in (2, 3):
+                raise ValueError("ImagePool: image %d is not a uint8 or uint16 array or tensor [h, w] or [h, w, C]" % k)
+            ts.append((t.unsqueeze(-1) if t.dim() == 2 else t).detach().cpu())
+        if not ts:
+            raise ValueError("ImagePool: the dataset is empty")
+        depths = {t.dtype for t in ts}
+        if len(depths) != 1:
+            raise ValueError("ImagePool: uint8 and uint16 images in one pool")
+        self = cls.__new__(cls)
+        self._start(device, max_bytes, None)
+        self._fill(len(ts), lambda i: ts[i].permute(2, 1, 0).contiguous(), 16 if ts[0].dtype == torch.uint16 else 8, white)
+        return self
+
+    def _start(self, device, max_bytes: int, files: Optional[List[str]]):
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.files, self.max_bytes = files, int(max_bytes)
+
+    def _read_headers(self, channels: int):
+        """-> (8 or 16, the samples of all files) from the files' headers; a folder of both depths is refused, naming a file of each"""
+        from PIL import Image
+        from ssdn.utils.data import image_bits
+        first, total = {}, 0
+        for f in self.files:
+            with Image.open(f) as im:
+                (w, h), b = im.size, image_bits(im.mode)
+            first.setdefault(b, f)
+            total += w * h * (channels or len(im.getbands()))
+        if len(first) == 2:
+            raise ValueError("ImagePool: 8-bit and 16-bit files in one folder (%s is 8-bit, %s is 16-bit): a pool is of one depth"
+                             % (first[8], first[16]))
+        return next(iter(first)), total
+
+    def _fill(self, n: int, read, bits: int, white: Optional[int]):
+        """pack read(0) .. read(n - 1), integer tensors [C, rows, cols] of `bits` bits per sample, and upload them"""
+        if bits == 16:
+            from ssdn.hip.engine import check_white
+            white = check_white(white, "ImagePool: white")
+        elif white is not None:
+            raise ValueError("ImagePool: white is the white level of a 16-bit pool and these images are 8-bit")
+        self.bits, self.white = bits, white
+        size = bits // 8
         images, sizes, total = [], [], 0
         for i in range(n):
-            img = dataset[i][0]
-            if img.dim() != 3:
-                raise ValueError("ImagePool: image %d is not a [C, rows, cols] tensor" % i)
+            img = read(i)
             if images and img.shape[0] != images[0].shape[0]:
                 raise ValueError("ImagePool: image %d has %d channel(s), image 0 has %d" % (i, img.shape[0], images[0].shape[0]))
-            u8 = (img * 255.0).round().clamp_(0, 255).to(torch.uint8).contiguous()
-            total += u8.numel()
-            sizes.append((u8.shape[1], u8.shape[2]))
+            total += img.numel() * size
+            sizes.append((img.shape[1], img.shape[2]))
             if total <= self.max_bytes:
-                images.append(u8)
+                images.append(img)
             elif len(images) > 1:
                 del images[1:]                      # over the cap: only the total is still wanted (image 0 keeps the channel count)
         self._check_cap(total, n)
         self.n, self.channels, self.nbytes = n, int(images[0].shape[0]), total
         self.sizes_host = torch.tensor(sizes, dtype=torch.int32).reshape(n, 2)
         per = self.sizes_host.to(torch.int64).prod(1) * self.channels
-        self.offsets_host = torch.cumsum(per, 0) - per                 # running sums: no alignment padding
-        host = torch.empty(total, dtype=torch.uint8)
-        for off, u8 in zip(self.offsets_host.tolist(), images):
-            host[off:off + u8.numel()] = u8.reshape(-1)
+        self.offsets_host = torch.cumsum(per, 0) - per                 # running sums in samples: no alignment padding
+        host = torch.empty(total // size, dtype=images[0].dtype)
+        for off, img in zip(self.offsets_host.tolist(), images):
+            host[off:off + img.numel()] = img.reshape(-1)
         del images
         self.pool = host.to(self.device)
         self.offsets, self.sizes = self.offsets_host.to(self.device), self.sizes_host.to(self.device)
@@ -82,15 +150,15 @@ class ImagePool:
         return self.n
 
     def image(self, i: int) -> torch.Tensor:
-        """image i as the pool holds it: a uint8 [C, rows, cols] view of the pool, on the pool's device"""
+        """image i as the pool holds it: a uint8 (16-bit pool: uint16) [C, rows, cols] view of the pool, on the pool's device"""
         rows, cols = (int(v) for v in self.sizes_host[i])
         off = int(self.offsets_host[i])
         return self.pool[off:off + self.channels * rows * cols].view(self.channels, rows, cols)
 
     def upright(self, i: int) -> torch.Tensor:
-        """image i as `Denoiser.denoise` and `Denoiser.estimate_noise` take it: uint8 [h, w, C] on the host (the dataset's tensors carry
-        the package's swapped axes: rows run along the picture's x)"""
-        return self.image(i).permute(2, 1, 0).contiguous().cpu()
+        """image i as `Denoiser.denoise` and `Denoiser.estimate_noise` take it: uint8 (16-bit pool: uint16) [h, w, C] on the host (the
+        dataset's tensors carry the package's swapped axes: rows run along the picture's x)"""
+        return self.image(i).cpu().permute(2, 1, 0).contiguous()
 
     def set_params(self, values) -> "ImagePool":
         """the per-image noise parameter table, fp32 [N] in the head's units"""
@@ -102,6 +170,9 @@ class ImagePool:
 
     def estimate_params(self, denoiser, kind: str, chunk: int = 64) -> "ImagePool":
         """fill the table with `Denoiser.estimate_noise`'s "noise_param" of every image (sigma / 255 for gauss, lambda for poisson)"""
+        if self.bits == 16:
+            from ssdn.hip.lib import NOISE_EST_BYTES_ONLY
+            raise ValueError("ImagePool: " + NOISE_EST_BYTES_ONLY)
         vals: List[float] = []
         for lo in range(0, self.n, chunk):
             est = denoiser.estimate_noise([self.upright(i) for i in range(lo, min(lo + chunk, self.n))], kind=kind)
@@ -271,7 +342,10 @@ class DevicePoolStream:
         coords = torch.empty((B, cells, 2), dtype=torch.int64, device=dev) if n2v else None
         origin = torch.empty((B, 3), dtype=torch.int32, device=dev) if self.keep_origin else None
         index = idx.to(torch.int32).to(dev, non_blocking=True)
-        a = L.PoolPatchArgs()
+        wide = pool.bits == 16
+        a = L.PoolPatch16Args() if wide else L.PoolPatchArgs()
+        if wide:
+            a.white = pool.white
         a.pool, a.offsets, a.sizes, a.index = pool.pool.data_ptr(), pool.offsets.data_ptr(), pool.sizes.data_ptr(), index.data_ptr()
         a.params = pool.params.data_ptr() if self.per_image else None
         a.noisy32 = inp.data_ptr()
@@ -284,7 +358,7 @@ class DevicePoolStream:
         a.seed, a.offset = self.seed, self._calls
         self._calls += 1
         rec = (L.OpRec * 1)()
-        rec[0].type, rec[0].lane, rec[0].args = L.OP["pool_patch"], 0, C.cast(C.pointer(a), C.c_void_p)
+        rec[0].type, rec[0].lane, rec[0].args = L.OP["pool_patch16" if wide else "pool_patch"], 0, C.cast(C.pointer(a), C.c_void_p)
         L.check(L.load().ssdn_run_ops(rec, 1, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         self.last_origin = origin
         return self._batch(idx, inp, plain, par, coords)
@@ -292,7 +366,7 @@ class DevicePoolStream:
     def _prepare_torch(self, idx: torch.Tensor):
         from ssdn.utils import n2v_ups
         pool, g, B, Cn, P = self.pool, self.generator, idx.numel(), self.pool.channels, self.patch_size
-        u8 = torch.empty((B, Cn, P, P), dtype=torch.uint8, device=self.device)
+        u8 = torch.empty((B, Cn, P, P), dtype=pool.pool.dtype, device=self.device)
         origin = torch.zeros((B, 3), dtype=torch.int32)
         for b, i in enumerate(idx.tolist()):
             rows, cols = (int(v) for v in pool.sizes_host[i])
@@ -303,7 +377,10 @@ class DevicePoolStream:
             u8[b] = cut_patch(pool.image(i), P, x0, y0, d)
         self._calls += 1
         self.last_origin = origin if self.keep_origin else None
-        plain = u8.to(torch.float32).div_(255.0)
+        if pool.bits == 16:                         # min(s, white) / white in fp32, as SSDN_OP_POOL_PATCH16
+            plain = u8.to(torch.int32).clamp_(max=pool.white).to(torch.float32).div_(float(pool.white))
+        else:
+            plain = u8.to(torch.float32).div_(255.0)
         inp, coords = plain, None
         if self.algorithm == NoiseAlgorithm.NOISE_TO_VOID:
             inp, coords = n2v_ups.manipulate_batch(plain, 5, generator=g)

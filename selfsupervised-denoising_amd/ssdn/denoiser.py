@@ -50,6 +50,7 @@ from torch.autograd.function import once_differentiable
 
 import ssdn
 from ssdn.datasets import NoisyDataset
+from ssdn.hip.lib import NOISE_EST_BYTES_ONLY
 from ssdn.models import NoiseNetwork
 from ssdn.params import ConfigValue, NoiseValue, Pipeline, PipelineOutput
 
@@ -430,7 +431,7 @@ class Denoiser(nn.Module):
         return float(v)
 
     def _denoise_images(self, images: List) -> List[Tensor]:
-        """`denoise`'s images as contiguous uint8 CPU tensors [h, w, C] of the model's channel count (ValueError otherwise)"""
+        """`denoise`'s images as contiguous uint8 or uint16 CPU tensors [h, w, C] of the model's channel count (ValueError otherwise)"""
         import numpy as np
         Cn = self.cfg[ConfigValue.IMAGE_CHANNELS]
         imgs = []
@@ -439,8 +440,8 @@ class Denoiser(nn.Module):
             if isinstance(im, np.ndarray):
                 a = np.ascontiguousarray(im)
                 t = torch.from_numpy(a if a.flags.writeable else a.copy())      # (PIL hands out read-only arrays)
-            if not torch.is_tensor(t) or t.dtype != torch.uint8 or t.dim() not in (2, 3):
-                raise ValueError("denoise: image %d is not a uint8 array or tensor [h, w] or [h, w, C]" % k)
+            if not torch.is_tensor(t) or t.dtype not in (torch.uint8, torch.uint16) or t.dim() not in (2, 3):
+                raise ValueError("denoise: image %d is not a uint8 or uint16 array or tensor [h, w] or [h, w, C]" % k)
             t = t.detach().cpu()
             t = (t.unsqueeze(-1) if t.dim() == 2 else t).contiguous()
             if t.shape[2] != Cn:
@@ -513,6 +514,8 @@ class Denoiser(nn.Module):
             raise ValueError("estimate_noise: kind must be 'gauss' or 'poisson', got %r" % (kind,))
         bucket, batch_size = self._denoise_options(bucket, batch_size)
         imgs = self._denoise_images(images)
+        if any(t.dtype == torch.uint16 for t in imgs):
+            raise ValueError("estimate_noise: " + NOISE_EST_BYTES_ONLY)
         res: List = [None] * len(imgs)
         if not imgs:
             return res
@@ -543,27 +546,33 @@ class Denoiser(nn.Module):
 
     _TILE_HEAD = 16             # the byte buffer of a tiled image starts with SSDN_OP_NOISE_EST's tables: offs int64 [1], ext int32 [2]
 
-    def _denoise_tiled(self, t: Tensor, T: int, O: int, value, kind: Optional[str], batch_size: int, std: bool) -> Dict:
+    def _denoise_tiled(self, t: Tensor, T: int, O: int, value, kind: Optional[str], batch_size: int, std: bool,
+                       white: Optional[int] = None) -> Dict:
         """One image larger than the tile, through the inference plan (B, T, T) in overlapping tiles (include/ssdn_hip.h, SSDN_OP_TILE_IN /
         SSDN_OP_TILE_OUT).  t: uint8 CPU tensor [h, w, C]; value: the noise parameter, None, or "auto" with `kind`
         the estimator's.  One pinned upload; per batch of at most `batch_size` tiles TILE_IN into the engine's input, the run, a device
         copy of its output into the tile store (with std also the posterior launch and a copy into a second store); then TILE_OUT, one
-        download and one synchronisation.  A store is Kx Ky C T^2 4 bytes.  -> {"out", "tiles", ["noise_std"], ["std"], ["noise_param"]}."""
+        download and one synchronisation.  A store is Kx Ky C T^2 4 bytes.  -> {"out", "tiles", ["noise_std"], ["std"], ["noise_param"]}.
+        A uint16 t (never with "auto") stages its samples behind the same 16-byte head and runs SSDN_OP_TILE_IN16 / SSDN_OP_TILE_OUT16 at
+        `white`; "out" is then uint16."""
         from ssdn.hip import lib as L
         from ssdn.hip import engine as E
         ssdn_pipe = self._pipeline == Pipeline.SSDN
         h, w, Cn = (int(v) for v in t.shape)
         Kx, Ky = L.tile_count(w, T, O), L.tile_count(h, T, O)
         n, nb, head, S = Kx * Ky, w * h * Cn, self._TILE_HEAD, T - O
+        wide = t.dtype == torch.uint16
+        size = 2 if wide else 1                              # bytes of a sample
         if nb >= 2 ** 31:
-            raise ValueError("denoise: an image of %d x %d x %d is beyond the 2^31 bytes the tile ops address" % (w, h, Cn))
-        host = self._tile_buffer("host_in", head + nb, torch.uint8, pinned=True)
-        dev = self._tile_buffer("dev_in", head + nb, torch.uint8)
+            raise ValueError("denoise: an image of %d x %d x %d is beyond the 2^31 %s the tile ops address"
+                             % (w, h, Cn, "samples" if wide else "bytes"))
+        host = self._tile_buffer("host_in", head + size * nb, torch.uint8, pinned=True)
+        dev = self._tile_buffer("dev_in", head + size * nb, torch.uint8)
         host[:8].view(torch.int64)[0] = 0
         host[8:16].view(torch.int32).copy_(torch.tensor([w, h], dtype=torch.int32))
-        host[head:head + nb] = t.reshape(-1)
-        dev[:head + nb].copy_(host[:head + nb], non_blocking=True)
-        img = dev[head:head + nb]
+        host[head:head + size * nb].view(t.dtype)[:] = t.reshape(-1)
+        dev[:head + size * nb].copy_(host[:head + size * nb], non_blocking=True)
+        img = dev[head:head + size * nb].view(t.dtype)
         auto = isinstance(value, str)
         if auto:
             # one estimate over the whole image (B = 1, a tensor of the image's own extent): Denoiser.estimate_noise's, whatever the tiling
@@ -580,7 +589,7 @@ class Denoiser(nn.Module):
         for k0 in range(0, n, batch_size):
             B = min(batch_size, n - k0)
             eng = self._engine(B, T, T, False)
-            data = [E.tile_in(img, w, h, T, O, k0, eng.inp)]
+            data = [E.tile_in(img, w, h, T, O, k0, eng.inp, white=white if wide else None)]
             if auto:                                         # broadcast on the device: no host round trip
                 eng.noise_param.copy_(par[:1].expand(B))
                 data += [torch.zeros(0), {NoisyDataset.Metadata.INPUT_NOISE_VALUES: eng.noise_param}]
@@ -598,9 +607,9 @@ class Denoiser(nn.Module):
                     else:
                         nstd.append(eng.noise_std[0 if self._const else b].clone())
         res: Dict = {"tiles": n}
-        dev_out = self._tile_buffer("dev_out", nb, torch.uint8)
-        host_out = self._tile_buffer("host_out", nb, torch.uint8, pinned=True)
-        E.tile_out(store, w, h, T, O, 0, dev_out)
+        dev_out = self._tile_buffer("dev_out", size * nb, torch.uint8)[:size * nb].view(t.dtype)
+        host_out = self._tile_buffer("host_out", size * nb, torch.uint8, pinned=True)[:size * nb].view(t.dtype)
+        E.tile_out(store, w, h, T, O, 0, dev_out, white=white if wide else None)
         host_out[:nb].copy_(dev_out[:nb], non_blocking=True)
         if std:
             dev_std = self._tile_buffer("dev_std", nb, torch.float32)
@@ -618,7 +627,7 @@ class Denoiser(nn.Module):
         return res
 
     def denoise(self, images: List, noise_param=None, batch_size: int = 1, bucket: Optional[int] = None, uniform: bool = False,
-                std: bool = False, tile: Optional[int] = None, overlap: Optional[int] = None) -> Dict:
+                std: bool = False, tile: Optional[int] = None, overlap: Optional[int] = None, white: Optional[int] = None) -> Dict:
         """Denoise already noisy images.  images: uint8 arrays or tensors [h, w] or [h, w, C], upright as PIL hands them out, of any and
         differing sizes, C the model's channel count.  Every image is reflection-padded bottom and right to a multiple of `bucket`
         (default and unit: NoiseNetwork.input_wh_mul(); larger values trade padding for fewer distinct plans -- at most _MAX_ENGINES are
@@ -647,6 +656,12 @@ class Denoiser(nn.Module):
         per-tile value (poisson: of each tile's map over the part of the tile inside the image); a model that estimates the noise level
         from its input (a variable unknown noise level: the sigma network) does so per TILE, a known difference from a whole-image run.
         With tile the result gains "tiles": Kx Ky per image, 1 for an image that was not tiled.
+        16-bit images (uint16 arrays or tensors; include/ssdn_hip.h, SSDN_OP_IMAGE_IN16): two bytes per sample
+        cross the bus, the value is min(sample, white) / white and "out" is uint16 of the input's shape -- clipped, * white, rounded to
+        nearest even.  white: the sample value that means 1.0, an integer in [1, 65535], None = 65535 (4095 for a 12-bit file); giving
+        it to a call without a uint16 image is a ValueError.  Images group by (dtype, padded shape): a call may mix both depths, and its
+        uint8 images come out exactly as from a call with only them.  A number as noise_param keeps its meaning (gauss 25: sigma =
+        25 / 255 of white); "auto" with a uint16 image is a ValueError before any device work: the estimator is defined on bytes.
         Like `posterior` it never becomes the forward that backward() / optimizer_step() / accumulate_metrics() act on."""
         ssdn_pipe = self._pipeline == Pipeline.SSDN
         value = self._noise_param_value(noise_param)
@@ -656,6 +671,14 @@ class Denoiser(nn.Module):
         bucket, batch_size = self._denoise_options(bucket, batch_size)
         imgs = self._denoise_images(images)
         auto = isinstance(value, str)                    # "auto": the value is estimated per image on the device
+        wide = [k for k, t in enumerate(imgs) if t.dtype == torch.uint16]
+        if white is not None:
+            from ssdn.hip.engine import check_white
+            white = check_white(white, "denoise: white")
+            if not wide:
+                raise ValueError("denoise: white is the white level of uint16 images and this call has none")
+        if auto and wide:
+            raise ValueError("denoise: noise_param 'auto' with a 16-bit image (image %d): %s" % (wide[0], NOISE_EST_BYTES_ONLY))
         res: Dict = {"out": [None] * len(imgs)}
         if auto:
             from ssdn.utils import noise
@@ -671,24 +694,29 @@ class Denoiser(nn.Module):
             return res
         tiled = [k for k, t in enumerate(imgs) if tile is not None and (t.shape[1] > tile or t.shape[0] > tile)]
         whole = [k for k in range(len(imgs)) if k not in tiled]
-        groups = self._denoise_groups(imgs, bucket, uniform, whole) if whole else {}
+        # by (dtype, padded shape): a batch is of one dtype, and `uniform` pads to the largest image of the same depth
+        groups = {}
+        for dt in (torch.uint8, torch.uint16):
+            same = [k for k in whole if imgs[k].dtype == dt]
+            if same:
+                groups.update({(dt,) + hw: m for hw, m in self._denoise_groups(imgs, bucket, uniform, same).items()})
         keep = (self._last_engine, getattr(self, "_has_loss_last", None))
         try:
             with torch.no_grad():
                 for k in tiled:
-                    one = self._denoise_tiled(imgs[k], tile, overlap, value, kind if auto else None, batch_size, std)
+                    one = self._denoise_tiled(imgs[k], tile, overlap, value, kind if auto else None, batch_size, std, white)
                     if auto and not math.isfinite(one["noise_param"]):
                         raise ValueError("denoise: image %d has too few valid 3x3 windows for a noise estimate (it is smaller "
                                          "than 3x3 or saturated): pass noise_param as a number" % k)
                     one["out"] = one["out"] if images[k].ndim == 3 else one["out"][:, :, 0]
                     for name, v in one.items():
                         res[name][k] = v
-                for (H, W), members in groups.items():
+                for (dt, H, W), members in groups.items():
                     for lo in range(0, len(members), batch_size):
                         idx = members[lo:lo + batch_size]
                         B = len(idx)
                         eng = self._engine(B, H, W, False)
-                        data = [eng.image_in([imgs[k] for k in idx])]
+                        data = [eng.image_in([imgs[k] for k in idx], white=white if dt == torch.uint16 else None)]
                         if auto:
                             # the estimates land in the engine's parameter tensor, which _run takes as it is: no host round trip
                             eng.estimate_noise(kind, into_noise_param=True)

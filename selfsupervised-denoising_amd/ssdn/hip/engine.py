@@ -48,12 +48,34 @@ def _tile_check(name: str, t: torch.Tensor, dtype, numel: int):
         raise L.SsdnHipError("%s must be a contiguous %s device tensor of at least %d elements" % (name, dtype, numel))
 
 
-def tile_in(img: torch.Tensor, w: int, h: int, T: int, O: int, k0: int, dst: torch.Tensor) -> torch.Tensor:
+def check_white(white, what: str = "white") -> int:
+    """`white` of the 16-bit ops (include/ssdn_hip.h): the uint16 sample value that means 1.0; None is the full range"""
+    if white is None:
+        return L.WHITE_MAX
+    if isinstance(white, bool) or int(white) != white or not 1 <= int(white) <= L.WHITE_MAX:
+        raise ValueError("%s must be an integer in [1, %d], got %r" % (what, L.WHITE_MAX, white))
+    return int(white)
+
+
+def tile_in(img: torch.Tensor, w: int, h: int, T: int, O: int, k0: int, dst: torch.Tensor, white: Optional[int] = None) -> torch.Tensor:
     """The tiles k0 .. k0 + B - 1 of one image into dst [B,C,T,T] (SSDN_OP_TILE_IN, csrc/tile_io.hip; the tiling is defined in
     include/ssdn_hip.h): one launch on torch's current stream that divides by 255, transposes to the package's swapped axes and reflects
     where a tile reaches past the image.  img: the image's bytes on the device, uint8 [h w C] upright and interleaved; dst: normally an
-    inference engine's `inp`, which `Denoiser._run` then takes without a copy.  Belongs to no engine: the image is not of a plan's shape."""
+    inference engine's `inp`, which `Denoiser._run` then takes without a copy.  Belongs to no engine: the image is not of a plan's shape.
+    A uint16 img runs SSDN_OP_TILE_IN16 (csrc/tile_io16.hip): min(sample, white) / white, white the sample value that means 1.0
+    (default 65535); white is refused for bytes."""
     B, Cn = int(dst.shape[0]), int(dst.shape[1])
+    if img.dtype == torch.uint16:
+        _tile_check("tile_in: img", img, torch.uint16, w * h * Cn)
+        _tile_check("tile_in: dst", dst, torch.float32, B * Cn * T * T)
+        if tuple(dst.shape) != (B, Cn, T, T):
+            raise L.SsdnHipError("tile_in: dst must be [B, C, %d, %d]" % (T, T))
+        a = L.TileIn16Args(_ptr(img), img.numel(), w, h, Cn, T, O, L.tile_count(w, T, O), L.tile_count(h, T, O), k0, B, check_white(white),
+                           _ptr(dst))
+        OpList([("tile_in16", a)]).run(current_stream())
+        return dst
+    if white is not None:
+        raise L.SsdnHipError("tile_in: white is for uint16 images")
     _tile_check("tile_in: img", img, torch.uint8, w * h * Cn)
     _tile_check("tile_in: dst", dst, torch.float32, B * Cn * T * T)
     if tuple(dst.shape) != (B, Cn, T, T):
@@ -63,15 +85,25 @@ def tile_in(img: torch.Tensor, w: int, h: int, T: int, O: int, k0: int, dst: tor
     return dst
 
 
-def tile_out(store: torch.Tensor, w: int, h: int, T: int, O: int, mode: int, dst: torch.Tensor) -> torch.Tensor:
+def tile_out(store: torch.Tensor, w: int, h: int, T: int, O: int, mode: int, dst: torch.Tensor, white: Optional[int] = None) -> torch.Tensor:
     """The tiles' values of one image blended back into that image (SSDN_OP_TILE_OUT): one launch on torch's current stream.  store:
     fp32 [Kx Ky, C, T, T] on the device; mode 0: dst uint8, the picture's bytes [h, w, C] (clipped, * 255, truncated); mode 1: dst fp32,
-    upright planes [C, h, w].  Only the first w h C elements of dst are written.  Does not synchronise."""
+    upright planes [C, h, w].  Only the first w h C elements of dst are written.  Does not synchronise.
+    A uint16 dst (mode 0 only) runs SSDN_OP_TILE_OUT16: the same blend, clipped, * white, rounded to nearest even (white: default 65535)."""
     Kx, Ky = L.tile_count(w, T, O), L.tile_count(h, T, O)
     Cn = int(store.shape[1])
     if tuple(store.shape) != (Kx * Ky, Cn, T, T):
         raise L.SsdnHipError("tile_out: store must be [%d, C, %d, %d]" % (Kx * Ky, T, T))
     _tile_check("tile_out: store", store, torch.float32, Kx * Ky * Cn * T * T)
+    if dst.dtype == torch.uint16:
+        if mode != 0:
+            raise L.SsdnHipError("tile_out: a uint16 dst takes mode 0 (the fp32 map is mode 1 into an fp32 dst)")
+        _tile_check("tile_out: dst", dst, torch.uint16, w * h * Cn)
+        a = L.TileOut16Args(_ptr(store), w, h, Cn, T, O, Kx, Ky, check_white(white), _ptr(dst), dst.numel())
+        OpList([("tile_out16", a)]).run(current_stream())
+        return dst
+    if white is not None:
+        raise L.SsdnHipError("tile_out: white is for a uint16 dst")
     _tile_check("tile_out: dst", dst, torch.float32 if mode else torch.uint8, w * h * Cn)
     a = L.TileOutArgs(_ptr(store), w, h, Cn, T, O, Kx, Ky, mode, _ptr(dst), dst.numel() * dst.element_size())
     OpList([("tile_out", a)]).run(current_stream())
@@ -750,15 +782,36 @@ class DenoiserEngine:
             buf["dev_out"] = torch.zeros((n,), dtype=torch.uint8, device=self.device)
         return buf
 
-    def image_in(self, images: List[torch.Tensor]) -> torch.Tensor:
+    def _image_buffers16(self):
+        """_image_buffers() for uint16 batches, allocated on the first such batch: the same head of tables (bytes), then the packed
+        samples, every image on a multiple of IMAGE_ALIGN samples.  Byte tensors: the samples are a uint16 view behind the head."""
+        buf = self._img
+        if "dev_in16" not in buf:
+            a = self.IMAGE_ALIGN
+            buf["head"] = (16 * self.B + a - 1) // a * a
+            n = buf["head"] + 2 * self.B * ((self.C * self.H * self.W + a - 1) // a * a)
+            buf["host_in16"] = torch.zeros((n,), dtype=torch.uint8).pin_memory()
+            buf["host_out16"] = torch.zeros((n,), dtype=torch.uint8).pin_memory()
+            buf["dev_in16"] = torch.zeros((n,), dtype=torch.uint8, device=self.device)
+            buf["dev_out16"] = torch.zeros((n,), dtype=torch.uint8, device=self.device)
+        return buf
+
+    def image_in(self, images: List[torch.Tensor], white: Optional[int] = None) -> torch.Tensor:
         """Fill `self.inp` with a batch of whole images (SSDN_OP_IMAGE_IN, csrc/image_io.hip): one pinned upload of the packed bytes and
         their tables, one launch that divides by 255, transposes to the package's swapped axes and reflection-pads every image bottom
         and right to the engine's shape.  images: exactly B contiguous uint8 CPU tensors [h, w, C] (upright, as PIL hands them out) with
         w <= H and h <= W of the engine (tensor axis 2 runs along x).  -> self.inp, which `Denoiser._run` then takes without a copy.
-        The tables stay on the device for the image_out() that follows."""
+        The tables stay on the device for the image_out() that follows.
+        A batch of uint16 tensors runs SSDN_OP_IMAGE_IN16 (csrc/image_io16.hip): two bytes per sample cross the bus, the value is
+        min(sample, white) / white with `white` the sample value that means 1.0 (default 65535; refused for bytes), and image_out()
+        then returns uint16 at the same white level.  A batch is of one dtype."""
         B, Cn = self.B, self.C
         if len(images) != B:
             raise L.SsdnHipError("image_in: %d images for an engine of batch %d" % (len(images), B))
+        if images[0].dtype == torch.uint16:
+            return self._image_in16(images, check_white(white))
+        if white is not None:
+            raise L.SsdnHipError("image_in: white is for uint16 images")
         for t in images:
             if (t.dtype != torch.uint8 or t.device.type != "cpu" or t.dim() != 3 or t.shape[2] != Cn or not t.is_contiguous()
                     or not (1 <= t.shape[1] <= self.H and 1 <= t.shape[0] <= self.W)):
@@ -775,17 +828,44 @@ class DenoiserEngine:
         host[8 * B:16 * B].view(torch.int32).copy_(torch.tensor([[t.shape[1], t.shape[0]] for t in images], dtype=torch.int32).reshape(-1))
         n = buf["head"] + pos
         buf["dev_in"][:n].copy_(host[:n], non_blocking=True)
-        buf["offs"], buf["shapes"], buf["bytes"] = offs, [tuple(t.shape) for t in images], pos
+        buf["offs"], buf["shapes"], buf["bytes"], buf["bits"] = offs, [tuple(t.shape) for t in images], pos, 8
         dev = buf["dev_in"]
         arg = L.ImageInArgs(_ptr(dev, buf["head"]), pos, _ptr(dev), _ptr(dev, 8 * B), B, Cn, self.H, self.W, _ptr(self.inp))
         OpList([("image_in", arg)]).run(current_stream())        # (behind the upload, on torch's current stream)
+        return self.inp
+
+    def _image_in16(self, images: List[torch.Tensor], white: int) -> torch.Tensor:
+        """image_in() for a batch of uint16 tensors; offsets and counts are in samples"""
+        B, Cn = self.B, self.C
+        for t in images:
+            if (t.dtype != torch.uint16 or t.device.type != "cpu" or t.dim() != 3 or t.shape[2] != Cn or not t.is_contiguous()
+                    or not (1 <= t.shape[1] <= self.H and 1 <= t.shape[0] <= self.W)):
+                raise L.SsdnHipError("image_in: every image of a uint16 batch must be a contiguous uint16 CPU tensor [h, w, %d] with "
+                                     "w <= %d and h <= %d" % (Cn, self.H, self.W))
+        buf = self._image_buffers16()
+        host, a, head = buf["host_in16"], self.IMAGE_ALIGN, buf["head"]
+        samples = host[head:].view(torch.uint16)
+        offs, pos = [], 0
+        for t in images:
+            offs.append(pos)
+            samples[pos:pos + t.numel()] = t.reshape(-1)
+            pos += (t.numel() + a - 1) // a * a
+        host[:8 * B].view(torch.int64).copy_(torch.tensor(offs, dtype=torch.int64))
+        host[8 * B:16 * B].view(torch.int32).copy_(torch.tensor([[t.shape[1], t.shape[0]] for t in images], dtype=torch.int32).reshape(-1))
+        n = head + 2 * pos
+        buf["dev_in16"][:n].copy_(host[:n], non_blocking=True)
+        buf["offs"], buf["shapes"], buf["bytes"], buf["bits"], buf["white"] = offs, [tuple(t.shape) for t in images], pos, 16, white
+        dev = buf["dev_in16"]
+        arg = L.ImageIn16Args(_ptr(dev, head), pos, _ptr(dev), _ptr(dev, 8 * B), B, Cn, self.H, self.W, white, _ptr(self.inp))
+        OpList([("image_in16", arg)]).run(current_stream())      # (behind the upload, on torch's current stream)
         return self.inp
 
     def image_out(self, x: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
         """The images of the last image_in() batch out of `x` (default: the denoised batch -- self.pme, the network output for the MSE
         pipelines) as bytes (SSDN_OP_IMAGE_OUT): one launch that crops to every extent, clips to [0, 1], multiplies by 255, truncates
         and transposes back, one download.  -> B uint8 CPU tensors [h, w, C]: views of the engine's pinned buffer, overwritten by the
-        next call.  Synchronises."""
+        next call.  Synchronises.  After a uint16 image_in(): SSDN_OP_IMAGE_OUT16 -- clip, * white, round to nearest even -- and uint16
+        tensors, at that batch's white level."""
         buf = self._img
         if "offs" not in buf:
             raise L.SsdnHipError("image_out: needs a preceding image_in()")
@@ -794,6 +874,14 @@ class DenoiserEngine:
         shape = (self.B, self.C, self.H, self.W)
         if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != shape or x.device != self.inp.device:
             raise L.SsdnHipError("image_out: x must be a contiguous fp32 [B,C,H,W] device tensor of the engine's shape")
+        if buf["bits"] == 16:
+            dev, n, head = buf["dev_in16"], buf["bytes"], buf["head"]
+            arg = L.ImageOut16Args(_ptr(x), _ptr(dev, 8 * self.B), _ptr(dev), _ptr(buf["dev_out16"]), n, *shape, buf["white"])
+            OpList([("image_out16", arg)]).run(current_stream())
+            buf["host_out16"][:2 * n].copy_(buf["dev_out16"][:2 * n], non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+            out = buf["host_out16"].view(torch.uint16)
+            return [out[o:o + h * w * c].view(h, w, c) for o, (h, w, c) in zip(buf["offs"], buf["shapes"])]
         dev, n = buf["dev_in"], buf["bytes"]
         arg = L.ImageOutArgs(_ptr(x), _ptr(dev, 8 * self.B), _ptr(dev), _ptr(buf["dev_out"]), n, *shape)
         OpList([("image_out", arg)]).run(current_stream())
@@ -811,6 +899,8 @@ class DenoiserEngine:
         buf = self._img
         if "offs" not in buf:
             raise L.SsdnHipError("estimate_noise: needs a preceding image_in()")
+        if buf["bits"] == 16:
+            raise L.SsdnHipError("estimate_noise: " + L.NOISE_EST_BYTES_ONLY)
         if kind not in L.NOISE_EST_KIND:
             raise L.SsdnHipError("estimate_noise: kind must be gauss or poisson, got %r" % (kind,))
         B = self.B

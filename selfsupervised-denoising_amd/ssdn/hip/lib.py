@@ -18,7 +18,7 @@ OP = dict(pack_input=1, conv=2, pool_fwd=3, pool_bwd=4, upsum_bwd=5, unrot_fwd=6
           wpack=10, grad_pack=11, head_ssdn=12, head_final=13, spatial_mean=14, mse=15, mask_mse=16, adam=17,
           metrics=18, zero=19, event_record=20, noise=21, input_grad=22, head_vjp=23,
           mse_vjp=24, accum=25, head_posterior=26, ssim=27, calibration=28, image_in=29, image_out=30, noise_est=31,
-          tile_in=32, tile_out=33, pool_patch=34)
+          tile_in=32, tile_out=33, pool_patch=34, image_in16=35, image_out16=36, tile_in16=37, tile_out16=38, pool_patch16=39)
 
 i32, f32, vp = C.c_int32, C.c_float, C.c_void_p
 
@@ -196,6 +196,9 @@ class NoiseEstArgs(C.Structure):
 
 NOISE_EST_CLASSES, NOISE_EST_BINS, NOISE_EST_NEST = 8, 1024, 20        # SSDN_NOISE_EST_* of include/ssdn_hip.h
 NOISE_EST_KIND = dict(gauss=0, poisson=1)
+# the refusal every 16-bit route gives where an estimate is asked for
+NOISE_EST_BYTES_ONLY = ("the noise-level estimator is defined on bytes (its classes, bins and validity test are in byte units): "
+                        "for 16-bit images pass the noise parameter as a number")
 
 
 class TileInArgs(C.Structure):
@@ -214,6 +217,36 @@ class PoolPatchArgs(C.Structure):
                 ("n2v_box", i32), ("n2v_radius", i32), ("seed", C.c_uint64), ("offset", C.c_uint64)]
 
 
+# the 16-bit siblings (ssdn_*16_args): counts and offsets in uint16 samples, `white` the sample value that means 1.0
+WHITE_MAX = 65535
+
+
+class ImageIn16Args(C.Structure):
+    _fields_ = [("src", vp), ("src_count", C.c_int64), ("offs", vp), ("ext", vp), ("B", i32), ("C", i32), ("H", i32), ("W", i32),
+                ("white", i32), ("dst", vp)]
+
+
+class ImageOut16Args(C.Structure):
+    _fields_ = [("x", vp), ("ext", vp), ("offs", vp), ("dst", vp), ("dst_count", C.c_int64), ("B", i32), ("C", i32), ("H", i32),
+                ("W", i32), ("white", i32)]
+
+
+class TileIn16Args(C.Structure):
+    _fields_ = [("src", vp), ("src_count", C.c_int64), ("w", i32), ("h", i32), ("C", i32), ("T", i32), ("O", i32), ("Kx", i32), ("Ky", i32),
+                ("k0", i32), ("B", i32), ("white", i32), ("dst", vp)]
+
+
+class TileOut16Args(C.Structure):
+    _fields_ = [("store", vp), ("w", i32), ("h", i32), ("C", i32), ("T", i32), ("O", i32), ("Kx", i32), ("Ky", i32), ("white", i32),
+                ("dst", vp), ("dst_count", C.c_int64)]
+
+
+class PoolPatch16Args(C.Structure):
+    _fields_ = [("pool", vp), ("offsets", vp), ("sizes", vp), ("params", vp), ("index", vp), ("noisy32", vp), ("ref32", vp), ("coords", vp),
+                ("param_out", vp), ("origin_out", vp), ("N", i32), ("B", i32), ("C", i32), ("P", i32), ("augment", i32),
+                ("n2v_box", i32), ("n2v_radius", i32), ("white", i32), ("seed", C.c_uint64), ("offset", C.c_uint64)]
+
+
 def tile_count(n: int, T: int, O: int) -> int:
     """K(n) of include/ssdn_hip.h (SSDN_OP_TILE_IN): the T-sized tiles of overlap O along an image axis of n elements"""
     return 1 if n <= T else -(-(n - O) // (T - O))
@@ -225,7 +258,9 @@ ARG_TYPES = dict(pack_input=PackInputArgs, conv=ConvArgs, pool_fwd=PoolArgs, poo
                  mse=MseArgs, mask_mse=MseArgs, adam=AdamArgs, metrics=MetricsArgs, zero=ZeroArgs, event_record=EventArgs, noise=NoiseArgs,
                  input_grad=InputGradArgs, head_vjp=HeadVjpArgs, mse_vjp=MseVjpArgs, accum=AccumArgs,
                  head_posterior=HeadPosteriorArgs, ssim=SsimArgs, calibration=CalibrationArgs, image_in=ImageInArgs, image_out=ImageOutArgs,
-                 noise_est=NoiseEstArgs, tile_in=TileInArgs, tile_out=TileOutArgs, pool_patch=PoolPatchArgs)
+                 noise_est=NoiseEstArgs, tile_in=TileInArgs, tile_out=TileOutArgs, pool_patch=PoolPatchArgs,
+                 image_in16=ImageIn16Args, image_out16=ImageOut16Args, tile_in16=TileIn16Args, tile_out16=TileOut16Args,
+                 pool_patch16=PoolPatch16Args)
 
 # every symbol include/ssdn_hip.h declares
 ABI_VERSION = 19      # SSDN_ABI_VERSION of include/ssdn_hip.h this binding mirrors

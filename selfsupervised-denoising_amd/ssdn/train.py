@@ -55,12 +55,16 @@ _PSNR_CACHE = "_psnr_per_sample"         # key of the per-sample PSNR values the
 NOISY_MODES = ("style", "auto")
 
 
-def check_noisy(cfg: Dict, noisy: Optional[str], augment: bool = False, pool_bytes: Optional[int] = None):
+def check_noisy(cfg: Dict, noisy: Optional[str], augment: bool = False, pool_bytes: Optional[int] = None, white: Optional[int] = None):
     """Training on images that are already noisy (`DenoiserTrainer.noisy`, `--noisy`): ValueError, with what to do instead, for every
     combination that cannot work.  noisy: None (off), "style" (the images carry the corruption NOISE_STYLE describes, its number is the
-    known parameter) or "auto" (the parameter of every image is estimated once, when the pool is built)."""
+    known parameter) or "auto" (the parameter of every image is estimated once, when the pool is built).  white (`--white`): the sample
+    value that means 1.0 in 16-bit training images, an integer in [1, 65535]; whether the images ARE 16-bit is known only when the pool
+    is built, which then refuses what does not fit (`--white` with 8-bit images, `--noisy auto` with 16-bit ones)."""
     from ssdn.utils import noise
     if not noisy:
+        if white is not None:
+            raise ValueError("--white is the white level of a 16-bit noisy-image pool: it needs --noisy")
         if augment:
             raise ValueError("--augment transforms the patches of the noisy-image pool: it needs --noisy")
         if pool_bytes is not None:
@@ -70,6 +74,8 @@ def check_noisy(cfg: Dict, noisy: Optional[str], augment: bool = False, pool_byt
         raise ValueError("noisy must be one of %s, got %r" % (", ".join(NOISY_MODES), noisy))
     if pool_bytes is not None and pool_bytes <= 0:
         raise ValueError("--pool_gb must be positive")
+    if white is not None and (isinstance(white, bool) or int(white) != white or not 1 <= int(white) <= 65535):
+        raise ValueError("--white must be an integer in [1, 65535], got %r" % (white,))
     algo, style = cfg[ConfigValue.ALGORITHM], cfg[ConfigValue.NOISE_STYLE]
     if algo not in POOL_ALGORITHMS:
         raise ValueError("--noisy: %s needs a clean image or a second realisation of every training image; train ssdn, ssdn_u_only or n2v "
@@ -159,6 +165,7 @@ class DenoiserTrainer:
         self.noisy: Optional[str] = None
         self.augment = False
         self.pool_bytes: Optional[int] = None
+        self.white: Optional[int] = None         # `--white`: the white level of a 16-bit pool (None: 65535); part of the "noisy" key only when given
 
     # ---- target -----------------------------------------------------------------------------------------------------------
     @property
@@ -556,6 +563,8 @@ class DenoiserTrainer:
             sd["device_stream"] = self.trainloader.state_dict()
         if self.noisy:                           # (an ordinary run's file keeps the key set it always had)
             sd["noisy"] = {"mode": self.noisy, "augment": bool(self.augment), "pool_bytes": self.pool_bytes}
+            if self.white is not None:           # (an 8-bit run's file keeps exactly its keys)
+                sd["noisy"]["white"] = int(self.white)
         if int(self.accumulate) > 1:             # (a K = 1 file keeps the key set it always had)
             sd["accumulate"] = int(self.accumulate)
         return sd
@@ -572,6 +581,7 @@ class DenoiserTrainer:
         self.accumulate = int(state_dict.get("accumulate", 1))
         noisy = state_dict.get("noisy") or {}
         self.noisy, self.augment, self.pool_bytes = noisy.get("mode"), bool(noisy.get("augment", False)), noisy.get("pool_bytes")
+        self.white = noisy.get("white")
         torch.set_rng_state(state_dict["rng"])
         if self.world > 1 and self.rank > 0:
             # the file holds rank 0's generator state: the other ranks continue from a state derived from it, not from a copy
@@ -617,12 +627,15 @@ class DenoiserTrainer:
         (DevicePoolStream): no DataLoader, no workers.  Without a GPU the same stream runs through torch."""
         from ssdn.utils import noise
         cfg = self.cfg
-        check_noisy(cfg, self.noisy, self.augment, self.pool_bytes)
+        check_noisy(cfg, self.noisy, self.augment, self.pool_bytes, self.white)
         child = self._open(cfg[ConfigValue.TRAIN_DATA_PATH], cfg[ConfigValue.TRAIN_DATASET_TYPE], None)
         dev = self.denoiser.device if self.denoiser is not None and hasattr(self.denoiser, "device") else \
             torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-        pool = ImagePool(child, dev, DEFAULT_POOL_BYTES if self.pool_bytes is None else int(self.pool_bytes))
+        pool = ImagePool(child, dev, DEFAULT_POOL_BYTES if self.pool_bytes is None else int(self.pool_bytes), white=self.white)
         logger.info("Noisy-image pool: %d images, %.1f MB on %s" % (len(pool), pool.nbytes / 1e6, dev))
+        if self.noisy == "auto" and pool.bits == 16:         # (only the built pool knows the depth)
+            from ssdn.hip.lib import NOISE_EST_BYTES_ONLY
+            raise ValueError("--noisy auto with 16-bit training images: %s (plain --noisy with the style's own parameter)" % NOISE_EST_BYTES_ONLY)
         if self.noisy == "auto":
             if self.denoiser is None or torch.device(dev).type != "cuda":
                 raise ValueError("--noisy auto estimates the noise levels on the device: it needs a GPU and the trainer's target")
@@ -645,7 +658,7 @@ class DenoiserTrainer:
         cfg = self.cfg
         if self.noisy:
             return self._noisy_train_data()
-        check_noisy(cfg, None, self.augment, self.pool_bytes)
+        check_noisy(cfg, None, self.augment, self.pool_bytes, self.white)
         crop = RandomCrop(cfg[ConfigValue.TRAIN_PATCH_SIZE], pad_if_needed=True, padding_mode="reflect")
         dataset = NoisyDataset(self._open(cfg[ConfigValue.TRAIN_DATA_PATH], cfg[ConfigValue.TRAIN_DATASET_TYPE], crop),
                                cfg[ConfigValue.NOISE_STYLE], cfg[ConfigValue.ALGORITHM], pad_uniform=False,

@@ -327,3 +327,42 @@ def set_color_channels(img, channels: int):
         if channels == 3:
             return img.convert("RGB")
     return img
+
+
+PIL_MODES_16 = ("I;16", "I;16L", "I;16B", "I;16N")
+
+
+def image_bits(mode: str) -> int:
+    """16 for the PIL modes `load_image` returns as uint16 (mode "I" included: a 16-bit file some decoders widen), else 8"""
+    return 16 if mode in PIL_MODES_16 or mode == "I" else 8
+
+
+def load_image(path: str, channels: int):
+    """An image file as the array `Denoiser.denoise` takes: uint8 [h, w, C] through `set_color_channels` for every file that is 8-bit, uint16
+    [h, w, 1] in host byte order for a 16-bit grey file (PIL modes I;16, I;16L, I;16B, I;16N, and I where every value lies in [0, 65535]:
+    ValueError otherwise).  `img.convert` clips such a file at 255, so it never goes that way; PIL cannot deliver 16-bit RGB, so a 16-bit
+    file with channels == 3 is refused -- arrays are the route for that."""
+    import numpy as np
+    from PIL import Image
+    with open(path, "rb") as f:
+        img = Image.open(f)
+        img.load()
+    if image_bits(img.mode) == 16:
+        if channels != 1:
+            raise ValueError("%s: 16-bit files are single-channel: use a model trained with --mono" % path)
+        a = np.asarray(img)
+        if img.mode == "I" and a.size and (a.min() < 0 or a.max() > 65535):
+            raise ValueError("%s: a 32-bit integer image with values outside [0, 65535] is not a 16-bit image" % path)
+        return np.ascontiguousarray(a.astype(np.uint16)).reshape(a.shape[0], a.shape[1], 1)
+    a = np.asarray(set_color_channels(img, channels), dtype=np.uint8)
+    return np.ascontiguousarray(a).reshape(a.shape[0], a.shape[1], -1)
+
+
+def save_image16(array, path: str):
+    """uint16 [h, w] or [h, w, 1] (array or tensor) -> a 16-bit grey image file (PIL mode I;16; exact through PNG and TIFF)"""
+    import numpy as np
+    from PIL import Image
+    a = array.numpy() if torch.is_tensor(array) else np.asarray(array)
+    if a.dtype != np.uint16 or not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 1)):
+        raise ValueError("save_image16: a uint16 array [h, w] or [h, w, 1] is needed, got %s %s" % (a.dtype, tuple(a.shape)))
+    Image.fromarray(np.ascontiguousarray(a.reshape(a.shape[0], a.shape[1]))).save(path)
