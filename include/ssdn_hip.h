@@ -881,9 +881,9 @@ typedef struct ssdn_pool_patch_args {
  *   POOL_PATCH16: image i is planar uint16 [C, rows_i, cols_i] at sample offsets[i]; value = in(sample).  The Philox draws, crop,
  *                 transform, Noise2Void selection, coords, param_out and origin_out are SSDN_OP_POOL_PATCH's: for equal (seed, offset,
  *                 sizes, index) the two ops give equal origin_out and coords.
- * Kernels (csrc/image_io16.hip, tile_io16.hip, patch_pool16.hip): the siblings' shapes -- one workgroup per
- * 32 x 64 patch with the transposition through an LDS tile of odd pitch holding fp32 or unsigned words (image and tile ops), one thread
- * per output pixel (pool op).
+ * Kernels: the siblings' own, in csrc/image_io.hip, tile_io.hip and patch_pool.hip -- each kernel is one template
+ * over the sample model (csrc/sample_io.h), instantiated for bytes and for uint16: one workgroup per 32 x 64 patch with the transposition
+ * through an LDS tile of odd pitch holding fp32 or unsigned words (image and tile ops), one thread per output pixel (pool op).
  * Argument errors are raised before any device call, the siblings' texts under the prefixes "image_in16:", "image_out16:", "tile_in16:",
  * "tile_out16:", "pool_patch16:", and "white must lie in [1, 65535]".  Adding these ops changed no existing struct: the ABI version
  * stays. */

@@ -156,11 +156,11 @@ int launch_noise_est(const ssdn_noise_est_args* a, hipStream_t s);             /
 int launch_tile_in(const ssdn_tile_in_args* a, hipStream_t s);                 // tile_io.hip: one uint8 image -> a batch of its overlapping fp32 tiles
 int launch_tile_out(const ssdn_tile_out_args* a, hipStream_t s);               // tile_io.hip: the fp32 tiles of one image -> that image, blended
 int launch_pool_patch(const ssdn_pool_patch_args* a, hipStream_t s);           // patch_pool.hip: a minibatch of training patches out of a device-resident image pool
-int launch_image_in16(const ssdn_image_in16_args* a, hipStream_t s);           // image_io16.hip: packed uint16 images -> the padded fp32 batch
-int launch_image_out16(const ssdn_image_out16_args* a, hipStream_t s);         // image_io16.hip: an fp32 batch -> packed uint16 images of each extent
-int launch_tile_in16(const ssdn_tile_in16_args* a, hipStream_t s);             // tile_io16.hip: one uint16 image -> a batch of its overlapping fp32 tiles
-int launch_tile_out16(const ssdn_tile_out16_args* a, hipStream_t s);           // tile_io16.hip: the fp32 tiles of one image -> that image as uint16, blended
-int launch_pool_patch16(const ssdn_pool_patch16_args* a, hipStream_t s);       // patch_pool16.hip: training patches out of a device-resident uint16 image pool
+int launch_image_in16(const ssdn_image_in16_args* a, hipStream_t s);           // image_io.hip: packed uint16 images -> the padded fp32 batch
+int launch_image_out16(const ssdn_image_out16_args* a, hipStream_t s);         // image_io.hip: an fp32 batch -> packed uint16 images of each extent
+int launch_tile_in16(const ssdn_tile_in16_args* a, hipStream_t s);             // tile_io.hip: one uint16 image -> a batch of its overlapping fp32 tiles
+int launch_tile_out16(const ssdn_tile_out16_args* a, hipStream_t s);           // tile_io.hip: the fp32 tiles of one image -> that image as uint16, blended
+int launch_pool_patch16(const ssdn_pool_patch16_args* a, hipStream_t s);       // patch_pool.hip: training patches out of a device-resident uint16 image pool
 int launch_mse_vjp(const ssdn_mse_vjp_args* a, hipStream_t s);
 int launch_adam(const ssdn_adam_args* a, hipStream_t s);
 #define ADAM_PACK_MAX 24

@@ -712,6 +712,7 @@ int launch_adam(const ssdn_adam_args* a, hipStream_t s) {
 // (seed, offset, s, e), so the Noise2Void replacement can RE-DERIVE the noisy value of the neighbour it copies (no second pass).
 // ------------------------------------------------------------------------------------------------
 #include "philox.h"        // Ph4, philox4x32_10, u01, ph_normal
+#include "sample_io.h"     // n2v_pick (shared with patch_pool.hip)
 enum { NS_INPUT = 0, NS_REF = 1, NS_PARAM = 2, NS_COORD = 3, NS_PARAM_REF = 4 };
 // noisy value of element e (channel plane index bc = b*C + c) of realisation `stream`
 static __device__ __forceinline__ float noise_apply(const ssdn_noise_args& a, float clean, float param, unsigned e, unsigned stream) {
@@ -735,19 +736,6 @@ static __device__ __forceinline__ float noise_param(const ssdn_noise_args& a, in
     if (a.p_lo == a.p_hi) return a.p_lo;
     const Ph4 r = philox4x32_10((unsigned)bc, stream, (unsigned)a.offset, (unsigned)(a.offset >> 32), (unsigned)a.seed, (unsigned)(a.seed >> 32));
     return a.p_lo + (a.p_hi - a.p_lo) * u01(r.v[0]);
-}
-// uniform integer over [lo, hi) without c (at least one candidate is assumed; n2v_ups.py:40-46); negative results wrap (Python indexing)
-static __device__ __forceinline__ int n2v_pick(int c, int r, int size, float u) {
-    const int lo = c - r < 0 ? c - r : 0, hi = c + r < size - 1 ? c + r : size - 1;
-    int span = hi - lo - (c >= lo && c < hi ? 1 : 0);
-    if (span < 1) span = 1;
-    int k = (int)(u * (float)span);
-    if (k >= span) k = span - 1;
-    int v = lo + k;
-    if (c >= lo && c < hi && v >= c) ++v;
-    if (v < 0) v += size;
-    if (v >= size) v = size - 1;
-    return v;
 }
 __global__ void k_noise(ssdn_noise_args a) {
     const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;

@@ -1,19 +1,16 @@
-// image_io.hip -- SSDN_OP_IMAGE_IN / SSDN_OP_IMAGE_OUT: whole images of differing sizes into and out of the engine as bytes (gfx950).
-// No planned list holds them.  Definition and contract: include/ssdn_hip.h; kernel shape and measurements: DESIGN.md section 3.16.
-// An image is upright uint8, row-major, channels interleaved (img[y][x][c], pitch w * C); the engine's tensors carry the image's x on axis 2
+// image_io.hip -- SSDN_OP_IMAGE_IN / SSDN_OP_IMAGE_OUT and SSDN_OP_IMAGE_IN16 / SSDN_OP_IMAGE_OUT16: whole images of differing sizes into
+// and out of the engine as bytes or as uint16 samples (gfx950).  No planned list holds them.  Definition and contract: include/ssdn_hip.h;
+// kernel shape and measurements: DESIGN.md section 3.16, the 16-bit sample model: section 3.20.
+// An image is upright, row-major, channels interleaved (img[y][x][c], pitch w * C); the engine's tensors carry the image's x on axis 2
 // and its y on axis 3 (the dataset classes' swapped H and W).  Both kernels fold that transposition through an LDS tile, so that both
-// global sides are coalesced: the bytes are touched along x, the fp32 planes along tensor axis 3.
-// k_image_in:  one workgroup per (TI x TJ tile of the PADDED tensor, sample): bytes -> / 255 -> LDS (a row per (x, c)) -> fp32 planes.
-// k_image_out: one workgroup per (TI x TJ tile of the EXTENT, sample): fp32 planes -> clip, * 255, truncate -> LDS -> bytes.
-// The tile is tile[(ii * C + c)][jj], pitch TJ + 1 words: the byte side walks its first index with consecutive lanes (odd pitch: a bank
+// global sides are coalesced: the samples are touched along x, the fp32 planes along tensor axis 3.
+// One definition of each kernel over the sample policy of sample_io.h (ByteSample: / 255, * 255 truncated; WideSample: / white, * white
+// rounded) and the op's argument struct A; counts, offsets and indices are in samples.
+// k_image_in:  one workgroup per (TI x TJ tile of the PADDED tensor, sample): samples -> Sample::in -> LDS (a row per (x, c)) -> fp32 planes.
+// k_image_out: one workgroup per (TI x TJ tile of the EXTENT, sample): fp32 planes -> Sample::out -> LDS -> samples.
+// The tile is tile[(ii * C + c)][jj], pitch TJ + 1 words: the sample side walks its first index with consecutive lanes (odd pitch: a bank
 // each), the plane side its second (consecutive words).
-#include "common.h"
-
-static constexpr int TI = 32, TJ = 64;                         // tile: tensor axis 2 (image x), tensor axis 3 (image y)
-static constexpr int IB = 256;                                 // threads of a block
-static constexpr int CMAX = 3;
-static_assert(TJ == 64 && IB % 64 == 0, "the plane side maps a wave's lanes to the 64 consecutive elements of one tile row");
-static_assert((TJ * TI) % IB == 0 && TI % (IB / 64) == 0, "every thread takes the same number of bytes and of plane elements");
+#include "sample_io.h"
 
 // a sample's extent, clamped to the tensor (ext is device memory: nothing on the host has seen it)
 static __device__ __forceinline__ void image_extent(const int32_t* ext, int b, int H, int W, int& e1, int& e2) {
@@ -21,30 +18,23 @@ static __device__ __forceinline__ void image_extent(const int32_t* ext, int b, i
     e2 = min(max(ext[2 * b + 1], 0), W);
 }
 
-// numpy's "reflect" for any pad length: index k >= 0 of an axis of n >= 1 elements continued without repeating its ends
-static __device__ __forceinline__ int reflect(int k, int n) {
-    if (k < n) return k;                                        // (inside the extent: most of a picture)
-    if (n == 1) return 0;
-    const int p = 2 * (n - 1), m = k % p;
-    return m < n ? m : p - m;
+// sample `idx` of the image at sample `off` lies inside the buffer of `count` samples (off is device memory too)
+static __device__ __forceinline__ bool image_inside(long long off, long long idx, long long count) {
+    return off >= 0 && off < count && idx < count - off;
 }
 
-// byte `idx` of the image at `off` lies inside the buffer of `bytes` bytes (off is device memory too)
-static __device__ __forceinline__ bool image_inside(long long off, long long idx, long long bytes) {
-    return off >= 0 && off < bytes && idx < bytes - off;
-}
-
-template <int C>
-__global__ __launch_bounds__(IB) void k_image_in(ssdn_image_in_args a) {
+template <class Sample, int C, class A>
+__global__ __launch_bounds__(IB) void k_image_in(A a) {
     __shared__ float tile[TI * CMAX][TJ + 1];
     const int b = blockIdx.z, i0 = blockIdx.y * TI, j0 = blockIdx.x * TJ;
     int e1, e2;
     image_extent(a.ext, b, a.H, a.W, e1, e2);
     const long long off = a.offs[b];
     const bool any = e1 > 0 && e2 > 0;                          // (block-uniform: a sample without an extent becomes zeros)
-    // bytes: consecutive lanes take consecutive (x, c) of one image row; every load of the thread is issued before the first is used
+    const Sample sm(a);
+    // samples: consecutive lanes take consecutive (x, c) of one image row; every load of the thread is issued before the first is used
     constexpr int NB = TJ * TI * C / IB;
-    unsigned char raw[NB];
+    typename Sample::T raw[NB];
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
         const int t = threadIdx.x + u * IB;
@@ -53,14 +43,14 @@ __global__ __launch_bounds__(IB) void k_image_in(ssdn_image_in_args a) {
         raw[u] = 0;
         if (any && i0 + ii < a.H && j0 + jj < a.W) {
             const long long idx = ((long long)reflect(j0 + jj, e2) * e1 + reflect(i0 + ii, e1)) * C + c;
-            if (image_inside(off, idx, a.src_bytes)) raw[u] = a.src[off + idx];
+            if (image_inside(off, idx, sample_count(a))) raw[u] = a.src[off + idx];
         }
     }
 #pragma unroll
     for (int u = 0; u < NB; ++u) {
         const int t = threadIdx.x + u * IB;
         const int jj = t / (TI * C), xb = t - jj * (TI * C);
-        tile[xb][jj] = (float)raw[u] / 255.f;                   // (a true division, like to_tensor's)
+        tile[xb][jj] = sm.in(raw[u]);
     }
     __syncthreads();
     // planes: a wave stores the 64 consecutive elements of one (c, i) row
@@ -73,21 +63,15 @@ __global__ __launch_bounds__(IB) void k_image_in(ssdn_image_in_args a) {
     }
 }
 
-// np.uint8(np.clip(v, 0, 1) * 255): a float32 product, then truncation; NaN -> 0
-static __device__ __forceinline__ unsigned quantise(float v) {
-    v = v > 0.f ? v : 0.f;                                      // (NaN and -0.0 end here)
-    v = v < 1.f ? v : 1.f;
-    return (unsigned)__fmul_rn(v, 255.f);
-}
-
-template <int C>
-__global__ __launch_bounds__(IB) void k_image_out(ssdn_image_out_args a) {
+template <class Sample, int C, class A>
+__global__ __launch_bounds__(IB) void k_image_out(A a) {
     __shared__ unsigned tile[TI * CMAX][TJ + 1];
     const int b = blockIdx.z, i0 = blockIdx.y * TI, j0 = blockIdx.x * TJ;
     int e1, e2;
     image_extent(a.ext, b, a.H, a.W, e1, e2);
     if (i0 >= e1 || j0 >= e2) return;                           // (block-uniform: the tile lies outside the extent)
     const long long off = a.offs[b];
+    const Sample sm(a);
     const int lane = threadIdx.x & 63, j = j0 + lane;
     // planes: every load of the thread is issued before the first is used
     constexpr int NP = TI * C / (IB / 64);
@@ -102,7 +86,7 @@ __global__ __launch_bounds__(IB) void k_image_out(ssdn_image_out_args a) {
     for (int u = 0; u < NP; ++u) {
         const int r = (threadIdx.x >> 6) + u * (IB / 64);
         const int c = r / TI, ii = r - c * TI;
-        tile[ii * C + c][lane] = quantise(v[u]);
+        tile[ii * C + c][lane] = sm.out(v[u]);
     }
     __syncthreads();
 #pragma unroll
@@ -112,34 +96,42 @@ __global__ __launch_bounds__(IB) void k_image_out(ssdn_image_out_args a) {
         const int ii = xb / C, c = xb - ii * C;
         if (i0 + ii < e1 && j0 + jj < e2) {
             const long long idx = ((long long)(j0 + jj) * e1 + (i0 + ii)) * C + c;
-            if (image_inside(off, idx, a.dst_bytes)) a.dst[off + idx] = (uint8_t)tile[xb][jj];
+            if (image_inside(off, idx, sample_count(a))) a.dst[off + idx] = (typename Sample::T)tile[xb][jj];
         }
     }
 }
 
-// the checks both ops share; `op` is the prefix of the error text
-static int image_io_check(const char* op, const void* bytes, long long nbytes, const void* offs, const void* ext, const void* planes,
-                          int B, int C, int H, int W) {
-    if (!bytes || !offs || !ext || !planes) return ssdn_set_error("%s: the byte buffer, offs, ext and the tensor must be given", op);
-    if (C != 1 && C != 3) return ssdn_set_error("%s: C must be 1 or 3", op);
-    if (B < 1 || H < 1 || W < 1) return ssdn_set_error("%s: B, H and W must be at least 1", op);
-    if (nbytes < 0) return ssdn_set_error("%s: the byte count must not be negative", op);
-    if (B > 65535 || (H + TI - 1) / TI > 65535) return ssdn_set_error("%s: B and the tile rows must be at most 65535", op);
+// the checks all four ops share; `op` is the prefix of the error text, `planes` the op's fp32 tensor
+template <class Sample, class A>
+static int image_io_check(const char* op, const A* a, const void* samples, const void* planes) {
+    if (!samples || !a->offs || !a->ext || !planes) return ssdn_set_error("%s: the %s buffer, offs, ext and the tensor must be given", op, Sample::noun);
+    if (a->C != 1 && a->C != 3) return ssdn_set_error("%s: C must be 1 or 3", op);
+    if (a->B < 1 || a->H < 1 || a->W < 1) return ssdn_set_error("%s: B, H and W must be at least 1", op);
+    if (sample_count(*a) < 0) return ssdn_set_error("%s: the %s count must not be negative", op, Sample::noun);
+    if (!Sample::white_ok(*a)) return ssdn_set_error("%s: white must lie in [1, 65535]", op);
+    if (a->B > 65535 || (a->H + TI - 1) / TI > 65535) return ssdn_set_error("%s: B and the tile rows must be at most 65535", op);
     return 0;
 }
 
-int launch_image_in(const ssdn_image_in_args* a, hipStream_t s) {
-    if (int rc = image_io_check("image_in", a->src, a->src_bytes, a->offs, a->ext, a->dst, a->B, a->C, a->H, a->W)) return rc;
+template <class Sample, class A>
+static int image_in(const char* op, const A* a, hipStream_t s) {
+    if (int rc = image_io_check<Sample>(op, a, a->src, a->dst)) return rc;
     const dim3 grid((unsigned)((a->W + TJ - 1) / TJ), (unsigned)((a->H + TI - 1) / TI), (unsigned)a->B);
-    if (a->C == 1) hipLaunchKernelGGL(k_image_in<1>, grid, dim3(IB), 0, s, *a);
-    else hipLaunchKernelGGL(k_image_in<3>, grid, dim3(IB), 0, s, *a);
+    if (a->C == 1) hipLaunchKernelGGL((k_image_in<Sample, 1, A>), grid, dim3(IB), 0, s, *a);
+    else hipLaunchKernelGGL((k_image_in<Sample, 3, A>), grid, dim3(IB), 0, s, *a);
     return 0;
 }
 
-int launch_image_out(const ssdn_image_out_args* a, hipStream_t s) {
-    if (int rc = image_io_check("image_out", a->dst, a->dst_bytes, a->offs, a->ext, a->x, a->B, a->C, a->H, a->W)) return rc;
+template <class Sample, class A>
+static int image_out(const char* op, const A* a, hipStream_t s) {
+    if (int rc = image_io_check<Sample>(op, a, a->dst, a->x)) return rc;
     const dim3 grid((unsigned)((a->W + TJ - 1) / TJ), (unsigned)((a->H + TI - 1) / TI), (unsigned)a->B);
-    if (a->C == 1) hipLaunchKernelGGL(k_image_out<1>, grid, dim3(IB), 0, s, *a);
-    else hipLaunchKernelGGL(k_image_out<3>, grid, dim3(IB), 0, s, *a);
+    if (a->C == 1) hipLaunchKernelGGL((k_image_out<Sample, 1, A>), grid, dim3(IB), 0, s, *a);
+    else hipLaunchKernelGGL((k_image_out<Sample, 3, A>), grid, dim3(IB), 0, s, *a);
     return 0;
 }
+
+int launch_image_in(const ssdn_image_in_args* a, hipStream_t s) { return image_in<ByteSample>("image_in", a, s); }
+int launch_image_out(const ssdn_image_out_args* a, hipStream_t s) { return image_out<ByteSample>("image_out", a, s); }
+int launch_image_in16(const ssdn_image_in16_args* a, hipStream_t s) { return image_in<WideSample>("image_in16", a, s); }
+int launch_image_out16(const ssdn_image_out16_args* a, hipStream_t s) { return image_out<WideSample>("image_out16", a, s); }

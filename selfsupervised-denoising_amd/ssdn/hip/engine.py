@@ -62,26 +62,22 @@ def tile_in(img: torch.Tensor, w: int, h: int, T: int, O: int, k0: int, dst: tor
     include/ssdn_hip.h): one launch on torch's current stream that divides by 255, transposes to the package's swapped axes and reflects
     where a tile reaches past the image.  img: the image's bytes on the device, uint8 [h w C] upright and interleaved; dst: normally an
     inference engine's `inp`, which `Denoiser._run` then takes without a copy.  Belongs to no engine: the image is not of a plan's shape.
-    A uint16 img runs SSDN_OP_TILE_IN16 (csrc/tile_io16.hip): min(sample, white) / white, white the sample value that means 1.0
-    (default 65535); white is refused for bytes."""
+    A uint16 img runs SSDN_OP_TILE_IN16 (the same kernel over uint16 samples): min(sample, white) / white, white the sample value that
+    means 1.0 (default 65535); white is refused for bytes."""
     B, Cn = int(dst.shape[0]), int(dst.shape[1])
-    if img.dtype == torch.uint16:
-        _tile_check("tile_in: img", img, torch.uint16, w * h * Cn)
-        _tile_check("tile_in: dst", dst, torch.float32, B * Cn * T * T)
-        if tuple(dst.shape) != (B, Cn, T, T):
-            raise L.SsdnHipError("tile_in: dst must be [B, C, %d, %d]" % (T, T))
-        a = L.TileIn16Args(_ptr(img), img.numel(), w, h, Cn, T, O, L.tile_count(w, T, O), L.tile_count(h, T, O), k0, B, check_white(white),
-                           _ptr(dst))
-        OpList([("tile_in16", a)]).run(current_stream())
-        return dst
-    if white is not None:
+    wide = img.dtype == torch.uint16
+    if white is not None and not wide:
         raise L.SsdnHipError("tile_in: white is for uint16 images")
-    _tile_check("tile_in: img", img, torch.uint8, w * h * Cn)
+    _tile_check("tile_in: img", img, torch.uint16 if wide else torch.uint8, w * h * Cn)
     _tile_check("tile_in: dst", dst, torch.float32, B * Cn * T * T)
     if tuple(dst.shape) != (B, Cn, T, T):
         raise L.SsdnHipError("tile_in: dst must be [B, C, %d, %d]" % (T, T))
-    a = L.TileInArgs(_ptr(img), img.numel(), w, h, Cn, T, O, L.tile_count(w, T, O), L.tile_count(h, T, O), k0, B, _ptr(dst))
-    OpList([("tile_in", a)]).run(current_stream())
+    image = (_ptr(img), img.numel(), w, h, Cn, T, O, L.tile_count(w, T, O), L.tile_count(h, T, O), k0, B)
+    if wide:
+        rec = ("tile_in16", L.TileIn16Args(*image, check_white(white), _ptr(dst)))
+    else:
+        rec = ("tile_in", L.TileInArgs(*image, _ptr(dst)))
+    OpList([rec]).run(current_stream())
     return dst
 
 
@@ -95,18 +91,18 @@ def tile_out(store: torch.Tensor, w: int, h: int, T: int, O: int, mode: int, dst
     if tuple(store.shape) != (Kx * Ky, Cn, T, T):
         raise L.SsdnHipError("tile_out: store must be [%d, C, %d, %d]" % (Kx * Ky, T, T))
     _tile_check("tile_out: store", store, torch.float32, Kx * Ky * Cn * T * T)
-    if dst.dtype == torch.uint16:
-        if mode != 0:
-            raise L.SsdnHipError("tile_out: a uint16 dst takes mode 0 (the fp32 map is mode 1 into an fp32 dst)")
-        _tile_check("tile_out: dst", dst, torch.uint16, w * h * Cn)
-        a = L.TileOut16Args(_ptr(store), w, h, Cn, T, O, Kx, Ky, check_white(white), _ptr(dst), dst.numel())
-        OpList([("tile_out16", a)]).run(current_stream())
-        return dst
-    if white is not None:
+    wide = dst.dtype == torch.uint16
+    if wide and mode != 0:
+        raise L.SsdnHipError("tile_out: a uint16 dst takes mode 0 (the fp32 map is mode 1 into an fp32 dst)")
+    if white is not None and not wide:
         raise L.SsdnHipError("tile_out: white is for a uint16 dst")
-    _tile_check("tile_out: dst", dst, torch.float32 if mode else torch.uint8, w * h * Cn)
-    a = L.TileOutArgs(_ptr(store), w, h, Cn, T, O, Kx, Ky, mode, _ptr(dst), dst.numel() * dst.element_size())
-    OpList([("tile_out", a)]).run(current_stream())
+    _tile_check("tile_out: dst", dst, torch.uint16 if wide else torch.float32 if mode else torch.uint8, w * h * Cn)
+    tiles = (_ptr(store), w, h, Cn, T, O, Kx, Ky)
+    if wide:
+        rec = ("tile_out16", L.TileOut16Args(*tiles, check_white(white), _ptr(dst), dst.numel()))
+    else:
+        rec = ("tile_out", L.TileOutArgs(*tiles, mode, _ptr(dst), dst.numel() * dst.element_size()))
+    OpList([rec]).run(current_stream())
     return dst
 
 
@@ -767,33 +763,21 @@ class DenoiserEngine:
 
     IMAGE_ALIGN = 16            # image_in(): every image of a batch starts on a multiple of this in the packed byte buffer
 
-    def _image_buffers(self):
-        """The byte buffers of image_in() / image_out(), sized for a full batch of un-padded images of the engine's shape: [offs: B int64 |
+    def _image_buffers(self, bits: int = 8):
+        """The buffers of image_in() / image_out(), sized for a full batch of un-padded images of the engine's shape: [offs: B int64 |
         ext: B x 2 int32 | the packed images], once pinned on the host and once on the device (one upload carries the tables and the
-        bytes), and the same pair for the images coming out."""
-        buf = self._img
-        if "dev_in" not in buf:
+        samples), and the same pair for the images coming out.  Byte tensors per sample depth, allocated on the first batch of that depth
+        (the uint16 batches' under the keys + "16"): the same head of tables, then the packed samples, every image on a multiple of
+        IMAGE_ALIGN samples; uint16 samples are a view behind the head."""
+        buf, k = self._img, "16" if bits == 16 else ""
+        if "dev_in" + k not in buf:
             a = self.IMAGE_ALIGN
             buf["head"] = (16 * self.B + a - 1) // a * a
-            n = buf["head"] + self.B * ((self.C * self.H * self.W + a - 1) // a * a)
-            buf["host_in"] = torch.zeros((n,), dtype=torch.uint8).pin_memory()
-            buf["host_out"] = torch.zeros((n,), dtype=torch.uint8).pin_memory()
-            buf["dev_in"] = torch.zeros((n,), dtype=torch.uint8, device=self.device)
-            buf["dev_out"] = torch.zeros((n,), dtype=torch.uint8, device=self.device)
-        return buf
-
-    def _image_buffers16(self):
-        """_image_buffers() for uint16 batches, allocated on the first such batch: the same head of tables (bytes), then the packed
-        samples, every image on a multiple of IMAGE_ALIGN samples.  Byte tensors: the samples are a uint16 view behind the head."""
-        buf = self._img
-        if "dev_in16" not in buf:
-            a = self.IMAGE_ALIGN
-            buf["head"] = (16 * self.B + a - 1) // a * a
-            n = buf["head"] + 2 * self.B * ((self.C * self.H * self.W + a - 1) // a * a)
-            buf["host_in16"] = torch.zeros((n,), dtype=torch.uint8).pin_memory()
-            buf["host_out16"] = torch.zeros((n,), dtype=torch.uint8).pin_memory()
-            buf["dev_in16"] = torch.zeros((n,), dtype=torch.uint8, device=self.device)
-            buf["dev_out16"] = torch.zeros((n,), dtype=torch.uint8, device=self.device)
+            n = buf["head"] + bits // 8 * self.B * ((self.C * self.H * self.W + a - 1) // a * a)
+            buf["host_in" + k] = torch.zeros((n,), dtype=torch.uint8).pin_memory()
+            buf["host_out" + k] = torch.zeros((n,), dtype=torch.uint8).pin_memory()
+            buf["dev_in" + k] = torch.zeros((n,), dtype=torch.uint8, device=self.device)
+            buf["dev_out" + k] = torch.zeros((n,), dtype=torch.uint8, device=self.device)
         return buf
 
     def image_in(self, images: List[torch.Tensor], white: Optional[int] = None) -> torch.Tensor:
@@ -802,49 +786,28 @@ class DenoiserEngine:
         and right to the engine's shape.  images: exactly B contiguous uint8 CPU tensors [h, w, C] (upright, as PIL hands them out) with
         w <= H and h <= W of the engine (tensor axis 2 runs along x).  -> self.inp, which `Denoiser._run` then takes without a copy.
         The tables stay on the device for the image_out() that follows.
-        A batch of uint16 tensors runs SSDN_OP_IMAGE_IN16 (csrc/image_io16.hip): two bytes per sample cross the bus, the value is
-        min(sample, white) / white with `white` the sample value that means 1.0 (default 65535; refused for bytes), and image_out()
-        then returns uint16 at the same white level.  A batch is of one dtype."""
+        A batch of uint16 tensors runs SSDN_OP_IMAGE_IN16 (the same kernel over uint16 samples; offsets and counts are then in samples):
+        two bytes per sample cross the bus, the value is min(sample, white) / white with `white` the sample value that means 1.0
+        (default 65535; refused for bytes), and image_out() then returns uint16 at the same white level.  A batch is of one dtype."""
         B, Cn = self.B, self.C
         if len(images) != B:
             raise L.SsdnHipError("image_in: %d images for an engine of batch %d" % (len(images), B))
-        if images[0].dtype == torch.uint16:
-            return self._image_in16(images, check_white(white))
-        if white is not None:
+        wide = images[0].dtype == torch.uint16
+        if wide:
+            white = check_white(white)
+        elif white is not None:
             raise L.SsdnHipError("image_in: white is for uint16 images")
+        bits, k, dtype = (16, "16", torch.uint16) if wide else (8, "", torch.uint8)
         for t in images:
-            if (t.dtype != torch.uint8 or t.device.type != "cpu" or t.dim() != 3 or t.shape[2] != Cn or not t.is_contiguous()
+            if (t.dtype != dtype or t.device.type != "cpu" or t.dim() != 3 or t.shape[2] != Cn or not t.is_contiguous()
                     or not (1 <= t.shape[1] <= self.H and 1 <= t.shape[0] <= self.W)):
-                raise L.SsdnHipError("image_in: every image must be a contiguous uint8 CPU tensor [h, w, %d] with w <= %d and h <= %d"
+                raise L.SsdnHipError(("image_in: every image of a uint16 batch must be a contiguous uint16 CPU tensor [h, w, %d] with "
+                                      "w <= %d and h <= %d" if wide else
+                                      "image_in: every image must be a contiguous uint8 CPU tensor [h, w, %d] with w <= %d and h <= %d")
                                      % (Cn, self.H, self.W))
-        buf = self._image_buffers()
-        host, a = buf["host_in"], self.IMAGE_ALIGN
-        offs, pos = [], 0
-        for t in images:
-            offs.append(pos)
-            host[buf["head"] + pos: buf["head"] + pos + t.numel()] = t.reshape(-1)
-            pos += (t.numel() + a - 1) // a * a
-        host[:8 * B].view(torch.int64).copy_(torch.tensor(offs, dtype=torch.int64))
-        host[8 * B:16 * B].view(torch.int32).copy_(torch.tensor([[t.shape[1], t.shape[0]] for t in images], dtype=torch.int32).reshape(-1))
-        n = buf["head"] + pos
-        buf["dev_in"][:n].copy_(host[:n], non_blocking=True)
-        buf["offs"], buf["shapes"], buf["bytes"], buf["bits"] = offs, [tuple(t.shape) for t in images], pos, 8
-        dev = buf["dev_in"]
-        arg = L.ImageInArgs(_ptr(dev, buf["head"]), pos, _ptr(dev), _ptr(dev, 8 * B), B, Cn, self.H, self.W, _ptr(self.inp))
-        OpList([("image_in", arg)]).run(current_stream())        # (behind the upload, on torch's current stream)
-        return self.inp
-
-    def _image_in16(self, images: List[torch.Tensor], white: int) -> torch.Tensor:
-        """image_in() for a batch of uint16 tensors; offsets and counts are in samples"""
-        B, Cn = self.B, self.C
-        for t in images:
-            if (t.dtype != torch.uint16 or t.device.type != "cpu" or t.dim() != 3 or t.shape[2] != Cn or not t.is_contiguous()
-                    or not (1 <= t.shape[1] <= self.H and 1 <= t.shape[0] <= self.W)):
-                raise L.SsdnHipError("image_in: every image of a uint16 batch must be a contiguous uint16 CPU tensor [h, w, %d] with "
-                                     "w <= %d and h <= %d" % (Cn, self.H, self.W))
-        buf = self._image_buffers16()
-        host, a, head = buf["host_in16"], self.IMAGE_ALIGN, buf["head"]
-        samples = host[head:].view(torch.uint16)
+        buf = self._image_buffers(bits)
+        host, a, head = buf["host_in" + k], self.IMAGE_ALIGN, buf["head"]
+        samples = host[head:].view(dtype)
         offs, pos = [], 0
         for t in images:
             offs.append(pos)
@@ -852,12 +815,16 @@ class DenoiserEngine:
             pos += (t.numel() + a - 1) // a * a
         host[:8 * B].view(torch.int64).copy_(torch.tensor(offs, dtype=torch.int64))
         host[8 * B:16 * B].view(torch.int32).copy_(torch.tensor([[t.shape[1], t.shape[0]] for t in images], dtype=torch.int32).reshape(-1))
-        n = head + 2 * pos
-        buf["dev_in16"][:n].copy_(host[:n], non_blocking=True)
-        buf["offs"], buf["shapes"], buf["bytes"], buf["bits"], buf["white"] = offs, [tuple(t.shape) for t in images], pos, 16, white
-        dev = buf["dev_in16"]
-        arg = L.ImageIn16Args(_ptr(dev, head), pos, _ptr(dev), _ptr(dev, 8 * B), B, Cn, self.H, self.W, white, _ptr(self.inp))
-        OpList([("image_in16", arg)]).run(current_stream())      # (behind the upload, on torch's current stream)
+        n = head + bits // 8 * pos
+        dev = buf["dev_in" + k]
+        dev[:n].copy_(host[:n], non_blocking=True)
+        buf["offs"], buf["shapes"], buf["bytes"], buf["bits"], buf["white"] = offs, [tuple(t.shape) for t in images], pos, bits, white
+        batch = (_ptr(dev, head), pos, _ptr(dev), _ptr(dev, 8 * B), B, Cn, self.H, self.W)
+        if wide:
+            rec = ("image_in16", L.ImageIn16Args(*batch, white, _ptr(self.inp)))
+        else:
+            rec = ("image_in", L.ImageInArgs(*batch, _ptr(self.inp)))
+        OpList([rec]).run(current_stream())                      # (behind the upload, on torch's current stream)
         return self.inp
 
     def image_out(self, x: Optional[torch.Tensor] = None) -> List[torch.Tensor]:
@@ -874,20 +841,16 @@ class DenoiserEngine:
         shape = (self.B, self.C, self.H, self.W)
         if x.dtype != torch.float32 or not x.is_contiguous() or tuple(x.shape) != shape or x.device != self.inp.device:
             raise L.SsdnHipError("image_out: x must be a contiguous fp32 [B,C,H,W] device tensor of the engine's shape")
-        if buf["bits"] == 16:
-            dev, n, head = buf["dev_in16"], buf["bytes"], buf["head"]
-            arg = L.ImageOut16Args(_ptr(x), _ptr(dev, 8 * self.B), _ptr(dev), _ptr(buf["dev_out16"]), n, *shape, buf["white"])
-            OpList([("image_out16", arg)]).run(current_stream())
-            buf["host_out16"][:2 * n].copy_(buf["dev_out16"][:2 * n], non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            out = buf["host_out16"].view(torch.uint16)
-            return [out[o:o + h * w * c].view(h, w, c) for o, (h, w, c) in zip(buf["offs"], buf["shapes"])]
-        dev, n = buf["dev_in"], buf["bytes"]
-        arg = L.ImageOutArgs(_ptr(x), _ptr(dev, 8 * self.B), _ptr(dev), _ptr(buf["dev_out"]), n, *shape)
-        OpList([("image_out", arg)]).run(current_stream())
-        buf["host_out"][:n].copy_(buf["dev_out"][:n], non_blocking=True)
+        wide = buf["bits"] == 16
+        k, size = ("16", 2) if wide else ("", 1)
+        dev, dev_out, host, n = buf["dev_in" + k], buf["dev_out" + k], buf["host_out" + k], buf["bytes"]
+        batch = (_ptr(x), _ptr(dev, 8 * self.B), _ptr(dev), _ptr(dev_out), n, *shape)
+        rec = ("image_out16", L.ImageOut16Args(*batch, buf["white"])) if wide else ("image_out", L.ImageOutArgs(*batch))
+        OpList([rec]).run(current_stream())
+        host[:size * n].copy_(dev_out[:size * n], non_blocking=True)
         torch.cuda.current_stream().synchronize()
-        return [buf["host_out"][o:o + h * w * c].view(h, w, c) for o, (h, w, c) in zip(buf["offs"], buf["shapes"])]
+        out = host.view(torch.uint16) if wide else host
+        return [out[o:o + h * w * c].view(h, w, c) for o, (h, w, c) in zip(buf["offs"], buf["shapes"])]
 
     def estimate_noise(self, kind: str, into_noise_param: bool = False) -> torch.Tensor:
         """A blind noise-level estimate of every image of the last image_in() batch (SSDN_OP_NOISE_EST, csrc/noise_est.hip) from the

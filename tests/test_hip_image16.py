@@ -1,5 +1,5 @@
-"""GPU: the five 16-bit ops -- SSDN_OP_IMAGE_IN16 / IMAGE_OUT16 (csrc/image_io16.hip), TILE_IN16 / TILE_OUT16 (csrc/tile_io16.hip),
-POOL_PATCH16 (csrc/patch_pool16.hip) -- against the numpy model of tests/image16_ref.py bit for bit, against their byte siblings at
+"""GPU: the five 16-bit ops -- SSDN_OP_IMAGE_IN16 / IMAGE_OUT16 (csrc/image_io.hip), TILE_IN16 / TILE_OUT16 (csrc/tile_io.hip),
+POOL_PATCH16 (csrc/patch_pool.hip) -- against the numpy model of tests/image16_ref.py bit for bit, against their byte siblings at
 white = 255, their guards; `Denoiser.denoise` on uint16 images against the host route sample for sample, whole and tiled; training from a
 16-bit pool; and `ssdn denoise` on a folder of both depths.
 
