@@ -85,7 +85,8 @@ enum ssdn_op_type {
     SSDN_OP_IMAGE_OUT16 = 36,   /* SSDN_OP_IMAGE_OUT writing uint16: clipped, * white, rounded to nearest even (no planned list holds it) */
     SSDN_OP_TILE_IN16 = 37,     /* SSDN_OP_TILE_IN from one uint16 image (no planned list holds it) */
     SSDN_OP_TILE_OUT16 = 38,    /* SSDN_OP_TILE_OUT's blend, quantised to uint16 [h][w][C] (no planned list holds it) */
-    SSDN_OP_POOL_PATCH16 = 39   /* SSDN_OP_POOL_PATCH over a planar uint16 pool (no planned list holds it) */
+    SSDN_OP_POOL_PATCH16 = 39,  /* SSDN_OP_POOL_PATCH over a planar uint16 pool (no planned list holds it) */
+    SSDN_OP_RISK = 40           /* per-sample reference-free risk statistics of the SSDN head's two outputs from the noisy image alone (no planned list holds it) */
 };
 
 /* One record of the op list.  `args` points at the matching ssdn_*_args struct (host memory).
@@ -683,6 +684,68 @@ typedef struct ssdn_calibration_args {
     void* scratch;                /* per-workgroup partial sums and counts (8 bytes each) */
     int64_t scratch_bytes;
 } ssdn_calibration_args;
+
+/* ---- SSDN_OP_RISK ------------------------------------------------------------------------------
+ * Judge a model without the clean image.  The blind-spot prior (mu_x, Sigma_x) at a pixel is a function of the OTHER pixels only, and for
+ * the gauss and poisson heads the delivered posterior mean is affine in the pixel's own noisy value: out = mu_x + W (y - mu_x),
+ * W = Sigma_x (Sigma_x + Sigma_n)^-1, W independent of y.  For zero-mean noise, independent across pixels and channels, of variance v_c:
+ *     E|mu_x - x|^2 = E[ |mu_x - y|^2 - sum_c v_c ]          E|out - x|^2 = E[ |out - y|^2 + sum_c (2 W_cc - 1) v_c ]
+ * (poisson: v_c = x_c / lambda has the unbiased stand-in y_c / lambda, W being independent of y_c).  The op adds the right-hand sides, the
+ * Gaussian negative log-likelihood terms of y under N(mu_x, Sigma_x + Sigma_n) and what a standard error needs, per sample over the
+ * margin-shrunk un-padded extent.  ssdn.utils.calculate_risk is the float64 specification; ssdn.utils.risk_values derives the reported
+ * values (PSNR estimates, standard errors, NLL).
+ * net_out, noisy, noise_param, est_raw, B, C, H, W, style, mode, diag are ssdn_head_posterior_args' and mean the same; style 2 (impulse:
+ * neither affine nor zero-mean) is an argument error.  pme [B,C,H,W]: the output actually delivered.  The kernel builds the
+ * specification's inputs itself, per pixel, widening the fp32 values to fp64 first:
+ *     mu = the first C planes of net_out;  Sigma_x = U U^T (sym3_uut's sums, left to right) or diag(a_c^2) with diag = 1 (C = 1: a^2);
+ *     n_c = sig^2 with head_sigma's rule: style 0: sig = (double)fmaxf(noise_param[b], 1e-3f) (mode 0) or (double)est, est head_est's fp32
+ *     softplus'd estimate;  style 1: n_c = (double)fmaxf(mu_c, 1e-3f) * f, f = 1 / (double)noise_param[b] (mode 0) or (double)est;
+ *     v^_c = n_c (style 0) or (double)y_c * f (style 1: the noisy value, unclipped, possibly negative).
+ * Then, T = Sigma_x + diag(n_c), d = y - mu, in this fixed order (C = 3; SSDN_OP_CALIBRATION's spelling for its S):
+ *     p0 = t00, l00 = sqrt(p0), l10 = t01 / l00, l20 = t02 / l00;   p1 = t11 - l10^2, l11 = sqrt(p1), l21 = (t12 - l20 l10) / l11;
+ *     p2 = t22 - l20^2 - l21^2, l22 = sqrt(p2);   w0 = d0 / l00, w1 = (d1 - l10 w0) / l11, w2 = (d2 - l20 w0 - l21 w1) / l22;
+ *     d2 = w0^2 + w1^2 + w2^2, logdet = ln p0 + ln p1 + ln p2;
+ *     Li00 = 1 / l00, Li11 = 1 / l11, Li22 = 1 / l22, Li10 = -(l10 Li00) / l11, Li21 = -(l21 Li11) / l22, Li20 = -(l20 Li00 + l21 Li10) / l22;
+ *     ti00 = Li00^2 + Li10^2 + Li20^2, ti11 = Li11^2 + Li21^2, ti22 = Li22^2 (the diagonal of T^-1);   W_cc = 1 - n_c ti_cc
+ *     (C = 1: p0 = s + n, W = 1 - n / p0, d2 = d^2 / p0, logdet = ln p0);
+ *     q_mu = sum_c (mu_c - y_c)^2 - sum_c v^_c,   q_out = sum_c (pme_c - y_c)^2 + sum_c (2 W_cc - 1) v^_c     (sums over c left to right).
+ * There is no 1e-6 regulariser here: the heads place theirs differently (none for C = 1), far below the estimator's resolution.
+ * A pixel is valid iff all of its inputs are finite and every pivot p_k > 0; otherwise it is degenerate: counted in stats[1] and left out
+ * of everything else.  Only the pixels margin <= i < e1 - margin, margin <= j < e2 - margin of ext[b] = (e1, e2) take part
+ * (SSDN_OP_METRICS' convention; NULL: the whole image; device memory, clamped to [0,H] x [0,W] by the kernel).  stats[b][12], fp64:
+ *     0: N, the valid pixels   1: the degenerate pixels   2: sum d2   3: sum logdet   4: sum |mu - y|^2   5: sum |pme - y|^2
+ *     6: sum sum_c v^_c   7: sum sum_c (2 W_cc - 1) v^_c   8: sum q_mu^2   9: sum q_out^2   10: sum tr W
+ *     11: the (valid pixel, channel) pairs with y_c <= 0 or y_c >= 1: clipped samples, where the noise is not zero-mean (reported, not removed)
+ * An empty region gives zeros.
+ * Arithmetic (csrc/risk.hip): one pixel per thread, the pixels of the margin-shrunk region numbered row-major,
+ * SSDN_RISK_BLOCK per workgroup (a function of ext and margin alone); fp64 with contraction off.  The eight floating-point sums go through
+ * a fixed shuffle tree per wave, then in wave order into the workgroup's scratch slot, the three counts as integers; a second launch adds
+ * a sample's slots in a fixed order.  stats[b] does not depend on the padding around the extent, on the other samples or on the launch
+ * being repeated.  scratch: device memory of SSDN_RISK_SCRATCH_BYTES(B, C, H, W) bytes, 8-byte aligned, contents irrelevant before and
+ * after; stats needs no initial contents either.
+ * Argument errors are raised before any device call (text prefixed "risk:"): net_out, noisy, pme, stats or scratch NULL, C not 1 or 3,
+ * B, H or W < 1, margin < 0, style not 0 or 1, mode not 0..2, mode 0 without noise_param or modes 1 / 2 without est_raw, diag not 0 or 1,
+ * scratch_bytes below the rule or scratch misaligned, B above 65535 or H * W above 2^31 - 1 - SSDN_RISK_BLOCK.
+ * Adding this op changed no existing struct: the ABI version stays. */
+#define SSDN_RISK_BLOCK 256
+#define SSDN_RISK_NSTATS 12
+#define SSDN_RISK_SCRATCH_BYTES(B, C, H, W) \
+    ((int64_t)8 * SSDN_RISK_NSTATS * (B) * (((int64_t)(H) * (W) + SSDN_RISK_BLOCK - 1) / SSDN_RISK_BLOCK))
+typedef struct ssdn_risk_args {
+    const float* net_out;     /* [B,Cout,H,W] */
+    const float* noisy;       /* [B,C,H,W] */
+    const float* noise_param; /* [B] (mode 0) */
+    const float* est_raw;     /* [1] (mode 1) or [B] (mode 2) */
+    const float* pme;         /* [B,C,H,W]: the output delivered */
+    const int32_t* ext;       /* [B][2] or NULL */
+    int32_t B, C, H, W;
+    int32_t style, mode;
+    int32_t diag;
+    int32_t margin;
+    double* stats;            /* out [B][12] */
+    void* scratch;            /* per-workgroup partial sums and counts (8 bytes each) */
+    int64_t scratch_bytes;
+} ssdn_risk_args;
 
 /* ---- SSDN_OP_IMAGE_IN / SSDN_OP_IMAGE_OUT ---------------------------------------------------------
  * Whole images of differing sizes into and out of the engine as bytes: what NoisyDataset.pad_to_output_size / unpad and

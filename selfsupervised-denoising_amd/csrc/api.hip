@@ -5,6 +5,8 @@
 #include <cstdio>
 #include <cstdlib>
 
+int launch_risk(const ssdn_risk_args* a, hipStream_t s);       // risk.hip: reference-free risk statistics, fp64 per pixel
+
 static thread_local char g_err[512] = "";
 thread_local hipEvent_t g_ssdn_stop_event = nullptr;
 thread_local bool g_ssdn_stop_used = false;
@@ -123,6 +125,7 @@ int ssdn_struct_size(int op_type) {
         case SSDN_OP_TILE_IN16: return (int)sizeof(ssdn_tile_in16_args);
         case SSDN_OP_TILE_OUT16: return (int)sizeof(ssdn_tile_out16_args);
         case SSDN_OP_POOL_PATCH16: return (int)sizeof(ssdn_pool_patch16_args);
+        case SSDN_OP_RISK: return (int)sizeof(ssdn_risk_args);
         default: return -1;
     }
 }
@@ -433,6 +436,7 @@ int ssdn_run_ops(const ssdn_op* ops, int n, void* stream) {
             case SSDN_OP_TILE_IN16: rc = launch_tile_in16((const ssdn_tile_in16_args*)p, s); break;
             case SSDN_OP_TILE_OUT16: rc = launch_tile_out16((const ssdn_tile_out16_args*)p, s); break;
             case SSDN_OP_POOL_PATCH16: rc = launch_pool_patch16((const ssdn_pool_patch16_args*)p, s); break;
+            case SSDN_OP_RISK: rc = launch_risk((const ssdn_risk_args*)p, s); break;
             case SSDN_OP_ZERO: {
                 const ssdn_zero_args* z = (const ssdn_zero_args*)p;
                 if (z->bytes & 15) return ssdn_set_error("op %d: zero size must be a multiple of 16", i);

@@ -60,6 +60,11 @@ class TrainCommand(Command):
         s.add_argument("--white", type=int, metavar="W",
                        help="[--noisy, 16-bit training images] The sample value that means 1.0: an integer in [1, 65535], default 65535; 4095 "
                             "for 12-bit camera files. The noise style's number is in units of white / 255.")
+        s.add_argument("--noisy_validation", metavar="PATH",
+                       help="[--noisy; ssdn with a gauss or poisson style] A folder or file of held-out images that are already noisy, of the "
+                            "pool's depth: at every eval_interval they are denoised and scored WITHOUT clean images -- psnr_out_est, "
+                            "psnr_mu_est (PSNR estimated from the noisy image alone) and nll_noisy in the VALID line and the valid/ scalars, "
+                            "the first output under val_imgs/. Independent of -v. A resumed run continues it.")
         r = actions.add_parser(self.RESUME_CMD, help="Resume the training of a model from the latest *.training file of a run directory.")
         r.add_argument("run_dir", help="Path to run directory to resume.")
         self._shared(r, False)
@@ -110,8 +115,9 @@ class TrainCommand(Command):
             trainer.noisy, trainer.augment = args.get("noisy"), bool(args.get("augment"))
             trainer.pool_bytes = int(args["pool_gb"] * 2 ** 30) if args.get("pool_gb") is not None else None
             trainer.white = args.get("white")
+            trainer.noisy_validation = args.get("noisy_validation")
             try:
-                check_noisy(cfg, trainer.noisy, trainer.augment, trainer.pool_bytes, trainer.white)
+                check_noisy(cfg, trainer.noisy, trainer.augment, trainer.pool_bytes, trainer.white, trainer.noisy_validation)
             except ValueError as e:
                 args["PARSER"].error(str(e))
         trainer.train()

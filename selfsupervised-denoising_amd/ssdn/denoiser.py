@@ -627,7 +627,8 @@ class Denoiser(nn.Module):
         return res
 
     def denoise(self, images: List, noise_param=None, batch_size: int = 1, bucket: Optional[int] = None, uniform: bool = False,
-                std: bool = False, tile: Optional[int] = None, overlap: Optional[int] = None, white: Optional[int] = None) -> Dict:
+                std: bool = False, tile: Optional[int] = None, overlap: Optional[int] = None, white: Optional[int] = None,
+                risk: bool = False, risk_margin: int = 16) -> Dict:
         """Denoise already noisy images.  images: uint8 arrays or tensors [h, w] or [h, w, C], upright as PIL hands them out, of any and
         differing sizes, C the model's channel count.  Every image is reflection-padded bottom and right to a multiple of `bucket`
         (default and unit: NoiseNetwork.input_wh_mul(); larger values trade padding for fewer distinct plans -- at most _MAX_ENGINES are
@@ -662,8 +663,23 @@ class Denoiser(nn.Module):
         it to a call without a uint16 image is a ValueError.  Images group by (dtype, padded shape): a call may mix both depths, and its
         uint8 images come out exactly as from a call with only them.  A number as noise_param keeps its meaning (gauss 25: sigma =
         25 / 255 of white); "auto" with a uint16 image is a ValueError before any device work: the estimator is defined on bytes.
+        risk=True (ssdn models with a gauss or poisson style; every other model raises NotImplementedError, as `risk` does) adds "risk":
+        per image a dict of Python floats, ssdn.utils.risk_values' -- "psnr_out_est" and "psnr_mu_est" estimate the PSNR of "out" and of
+        the prior mean against the clean image nobody has, "nll" is the negative log-likelihood of the noisy pixels under the model (see
+        `risk` for the rest and for the caveats: clipping, padded borders, a wrong noise parameter) -- over the image's extent shrunk by
+        risk_margin pixels on every side; an image of at most 2 risk_margin pixels in an axis has NaN values.  SSDN_OP_RISK runs between
+        the inference run and SSDN_OP_IMAGE_OUT and its statistics are read behind the synchronisation the download already has: "out"
+        is byte for byte what it is without the flag.  With "auto" the op reads the parameter the estimator wrote.  risk=True with tile=
+        is a ValueError: overlapping tiles would count pixels twice.
         Like `posterior` it never becomes the forward that backward() / optimizer_step() / accumulate_metrics() act on."""
         ssdn_pipe = self._pipeline == Pipeline.SSDN
+        if risk:
+            self.check_risk("denoise: risk=True")
+            if tile is not None:
+                raise ValueError("denoise: risk=True with tile= is not supported: overlapping tiles would count pixels twice")
+            risk_margin = int(risk_margin)
+            if risk_margin < 0:
+                raise ValueError("denoise: risk_margin must be at least 0, got %d" % risk_margin)
         value = self._noise_param_value(noise_param)
         tile, overlap = self._tile_options(tile, overlap)
         if std and not ssdn_pipe:
@@ -690,6 +706,8 @@ class Denoiser(nn.Module):
             res["std"] = [None] * len(imgs)
         if tile is not None:
             res["tiles"] = [1] * len(imgs)
+        if risk:
+            res["risk"] = [None] * len(imgs)
         if not imgs:
             return res
         tiled = [k for k, t in enumerate(imgs) if tile is not None and (t.shape[1] > tile or t.shape[0] > tile)]
@@ -724,7 +742,12 @@ class Denoiser(nn.Module):
                         elif value is not None:
                             data += [torch.zeros(0), {NoisyDataset.Metadata.INPUT_NOISE_VALUES: torch.full((B, 1, 1, 1), value)}]
                         self._run(data, clone=False)         # (no_grad: the inference plan of this shape, whose input is already in place)
+                        rstats = eng.risk(eng.image_extents(), risk_margin) if risk else None
                         outs = eng.image_out()
+                        if risk:                             # (image_out has synchronised)
+                            vals = ssdn.utils.risk_values(rstats.cpu(), eng.C)
+                            for b, k in enumerate(idx):
+                                res["risk"][k] = {name: float(v[b]) for name, v in vals.items()}
                         if auto:                             # (image_out has synchronised)
                             used = eng.noise_param.cpu()
                             for b, k in enumerate(idx):
@@ -935,6 +958,52 @@ class Denoiser(nn.Module):
             res["hist"] = dhist.cpu()
         if maps:
             res["zmap"] = dmap.cpu()
+        return res
+
+    def check_risk(self, who: str = "Denoiser.risk") -> None:
+        """Raise NotImplementedError unless this model has the reference-free risk estimate (`risk`): the SSDN pipeline with a gauss or
+        poisson noise style.  Decided from the configuration alone, before any device work."""
+        if self._pipeline != Pipeline.SSDN:
+            raise NotImplementedError("%s: the %s pipeline has no reference-free risk estimate (SSDN pipeline only): ssdn_u_only has no "
+                                      "head and so no noise variance, and the output of an MSE pipeline depends on the pixel itself, so it "
+                                      "would need a divergence estimate" % (who, self._pipeline.value))
+        from ssdn.utils import noise
+        kind = noise.parse_style(self.cfg[ConfigValue.NOISE_STYLE])[0]
+        if kind not in ("gauss", "poisson"):
+            raise NotImplementedError("%s: no reference-free risk estimate for an %s model: its posterior mean is not affine in the pixel "
+                                      "and its noise is not zero-mean (gauss and poisson models only)" % (who, kind))
+
+    def risk(self, data: List, margin: int = 16) -> Dict[str, Tensor]:
+        """A reference-free estimate of the error of the LAST `run_pipeline` / `train_step` batch (`data` = its inputs), per sample over
+        its un-padded extent shrunk by `margin` pixels on all four sides -- no clean image is read (ssdn.utils.calculate_risk is the
+        definition, ssdn.utils.risk_values the reported values).  -> host float64 [B] tensors "mse_mu_est" / "mse_out_est" (unbiased
+        estimates of the mean squared error of IMG_MU and IMG_DENOISED against the clean image), "psnr_mu_est" / "psnr_out_est" (NaN where
+        the estimate is <= 0: it is unbiased, not positive), "mse_mu_se" / "mse_out_se" (naive standard errors), "nll" (nats per
+        pixel-channel of the NOISY image under the model's marginal), "weight" (how much of its own noisy value a pixel's output keeps),
+        "clipped" (share of samples at or beyond 0 / 1, where the noise is not zero-mean), "degenerate", and the raw "stats" [B,12].  The
+        extent comes from the batch's metadata (Metadata.IMAGE_SHAPE), or is the whole image when there is none.  margin: a pixel near a
+        reflection-padded edge has a copy of itself inside the network's field of view, so the estimate is optimistic there; an extent of
+        at most 2 margin in an axis has N = 0 and NaN values.  The estimate inherits an error of the noise parameter given to a
+        known-noise model: a sigma that is too large reads as a better PSNR.  On a GPU two launches behind the last forward
+        (SSDN_OP_RISK, csrc/risk.hip: fp64 per pixel).  Reads only: outputs, metric accumulators, weights, plans and the last engines
+        stay what they were.  Synchronises.  SSDN pipeline with a gauss or poisson style (every NOISE_VALUE mode, full and diagonal
+        covariance); every other model raises NotImplementedError."""
+        self.check_risk()
+        margin = int(margin)
+        if margin < 0:
+            raise ValueError("risk(): margin must be at least 0, got %d" % margin)
+        eng = self._last_engine
+        if eng is None:
+            raise RuntimeError("risk() needs a preceding run_pipeline()")
+        meta = data[NoisyDataset.METADATA] if len(data) > NoisyDataset.METADATA else None
+        ext = None
+        shp = meta.get(NoisyDataset.Metadata.IMAGE_SHAPE) if isinstance(meta, dict) else None
+        if shp is not None:
+            shp = torch.as_tensor(shp).reshape(eng.B, -1)[:, -2:].to(torch.int32)
+            ext = shp.to(self.device).contiguous()
+        stats = eng.risk(ext, margin).cpu()                      # (synchronises: the launches have run, the buffers are free for the next)
+        res = dict(ssdn.utils.risk_values(stats, eng.C))
+        res["stats"] = stats
         return res
 
     def reset_device_metrics(self, kind: str = "train"):

@@ -1,7 +1,7 @@
 """`DenoiserEvaluator` -- evaluation driver (drop-in for /root/reference/ssdn/ssdn/eval.py:18-125): load a `.wt` or `.training`
 file, pad every test image by reflection to a x32 multiple / square / uniform size (Kodak 768x768, BSD300 512x512), run the
 forward kernels, un-pad, per-image PSNR -> `psnrs.csv` (with `ssim` set: per-image SSIM -> `ssims.csv`; with `calibration` set:
-per-image posterior calibration -> `calibration.csv`, the z-score histogram of the whole evaluation -> `calibration_hist.csv`), images -> `eval_imgs/`.  Reference defect fixed: `runs_dir` is honoured
+per-image reference-free risk estimate with `risk` set -> `risk.csv`; per-image posterior calibration -> `calibration.csv`, the z-score histogram of the whole evaluation -> `calibration_hist.csv`), images -> `eval_imgs/`.  Reference defect fixed: `runs_dir` is honoured
 (eval.py:32-35 drops it)."""
 import logging
 import os
@@ -14,7 +14,7 @@ from ssdn.cfg import DEFAULT_RUN_DIR
 from ssdn.datasets import NoisyDataset
 from ssdn.denoiser import Denoiser
 from ssdn.params import PipelineOutput
-from ssdn.train import _CALIB_CACHE, _SSIM_CACHE, DenoiserTrainer
+from ssdn.train import _CALIB_CACHE, _RISK_CACHE, _SSIM_CACHE, DenoiserTrainer
 
 logger = logging.getLogger("ssdn.eval")
 
@@ -93,6 +93,14 @@ class DenoiserEvaluator(DenoiserTrainer):
                         f.write(",".join(["id"] + names) + "\n")
                     for i in range(n):
                         f.write(",".join(["{:04d}".format(output_0_index + i)] + ["{:.6f}".format(float(cal[k][i])) for k in names]) + "\n")
+            rk = outputs.get(_RISK_CACHE)
+            if rk is not None:                  # `ssdn eval --risk`: the same rows, the reference-free risk estimate
+                names = list(ssdn.utils.data.RISK_VALUES)
+                with open(os.path.join(self.run_dir_path, "risk.csv"), "a") as f:
+                    if output_0_index == 0:
+                        f.write(",".join(["id"] + names) + "\n")
+                    for i in range(n):
+                        f.write(",".join(["{:04d}".format(output_0_index + i)] + ["{:.6f}".format(float(rk[k][i])) for k in names]) + "\n")
         return callback
 
     def save_calibration_hist(self) -> None:

@@ -420,6 +420,7 @@ class DenoiserEngine:
         self._post = {}             # posterior(): cov / std / samples buffers, allocated on first use (no plan tensor)
         self._ssim = {}             # ssim(): value / map / scratch buffers, allocated on first use (no plan tensor)
         self._calib = {}            # calibration(): stats / hist / zmap / scratch buffers, allocated on first use (no plan tensor)
+        self._risk = {}             # risk(): stats / scratch buffers, allocated on first use (no plan tensor)
         self._img = {}              # image_in() / image_out() / estimate_noise(): pinned and device byte buffers with their tables, allocated on first use (no plan tensor)
 
     # ---- op construction -----------------------------------------------------------------------------------
@@ -761,6 +762,32 @@ class DenoiserEngine:
         OpList([("calibration", a)]).run(s)
         return buf["stats"], (buf["hist"] if want_hist else None), (buf["zmap"] if want_map else None)
 
+    def risk(self, ext: Optional[torch.Tensor] = None, margin: int = 0, stream=None):
+        """Reference-free risk statistics of the LAST forward (SSDN_OP_RISK, csrc/risk.hip) per sample over its margin-shrunk un-padded
+        extent: two launches on the engine's stream behind that forward, reading its net_out, input, noise parameter / estimate and
+        self.pme -- no clean image.  ext: int32 [B,2] device tensor or None, accumulate_metrics' convention.  -> stats [B,12] float64
+        (ssdn.utils.risk_values derives the reported values): the engine's own buffer, allocated on first use outside the plan's tensors
+        and overwritten by the next call.  Nothing is synchronised."""
+        if self.pipeline != "ssdn":
+            raise NotImplementedError("the risk estimate exists for the ssdn pipeline only")
+        if self.style not in ("gauss", "poisson"):
+            raise NotImplementedError("the risk estimate needs a gauss or poisson model: the %s posterior mean is not affine in the pixel "
+                                      "and its noise is not zero-mean" % self.style)
+        shape = (self.B, self.C, self.H, self.W)
+        buf = self._risk
+        if "stats" not in buf:
+            buf["stats"] = torch.zeros((self.B, L.RISK_NSTATS), dtype=torch.float64, device=self.device)
+            buf["scratch"] = torch.zeros((L.risk_scratch_bytes(*shape) // 8,), dtype=torch.float64, device=self.device)
+        if self.mode == "var":
+            est_ptr = _ptr(self.est_raw)
+        else:
+            est_ptr = _ptr(self.params, 4 * self.est_off) if self.mode == "const" else None
+        a = L.RiskArgs(_ptr(self.main.tensor("out32")), _ptr(self.inp), _ptr(self.noise_param), est_ptr, _ptr(self.pme),
+                       _ptr(ext) if ext is not None else None, *shape, STYLE[self.style], MODE[self.mode], int(self.diag), int(margin),
+                       _ptr(buf["stats"]), _ptr(buf["scratch"]), buf["scratch"].numel() * 8)
+        OpList([("risk", a)]).run(current_stream() if stream is None else stream)
+        return buf["stats"]
+
     IMAGE_ALIGN = 16            # image_in(): every image of a batch starts on a multiple of this in the packed byte buffer
 
     def _image_buffers(self, bits: int = 8):
@@ -851,6 +878,15 @@ class DenoiserEngine:
         torch.cuda.current_stream().synchronize()
         out = host.view(torch.uint16) if wide else host
         return [out[o:o + h * w * c].view(h, w, c) for o, (h, w, c) in zip(buf["offs"], buf["shapes"])]
+
+    def image_extents(self) -> torch.Tensor:
+        """The un-padded extents (w_b, h_b) of the last image_in() batch as the ops read them: an int32 [B,2] view of the table that batch
+        left on the device (SSDN_OP_METRICS' convention)."""
+        buf = self._img
+        if "offs" not in buf:
+            raise L.SsdnHipError("image_extents: needs a preceding image_in()")
+        dev = buf["dev_in" + ("16" if buf["bits"] == 16 else "")]
+        return dev[8 * self.B:16 * self.B].view(torch.int32).view(self.B, 2)
 
     def estimate_noise(self, kind: str, into_noise_param: bool = False) -> torch.Tensor:
         """A blind noise-level estimate of every image of the last image_in() batch (SSDN_OP_NOISE_EST, csrc/noise_est.hip) from the

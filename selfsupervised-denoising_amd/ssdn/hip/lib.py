@@ -18,7 +18,7 @@ OP = dict(pack_input=1, conv=2, pool_fwd=3, pool_bwd=4, upsum_bwd=5, unrot_fwd=6
           wpack=10, grad_pack=11, head_ssdn=12, head_final=13, spatial_mean=14, mse=15, mask_mse=16, adam=17,
           metrics=18, zero=19, event_record=20, noise=21, input_grad=22, head_vjp=23,
           mse_vjp=24, accum=25, head_posterior=26, ssim=27, calibration=28, image_in=29, image_out=30, noise_est=31,
-          tile_in=32, tile_out=33, pool_patch=34, image_in16=35, image_out16=36, tile_in16=37, tile_out16=38, pool_patch16=39)
+          tile_in=32, tile_out=33, pool_patch=34, image_in16=35, image_out16=36, tile_in16=37, tile_out16=38, pool_patch16=39, risk=40)
 
 i32, f32, vp = C.c_int32, C.c_float, C.c_void_p
 
@@ -179,6 +179,20 @@ def calib_scratch_bytes(B: int, Cn: int, H: int, W: int) -> int:
     return 8 * CALIB_NSTATS * B * ((H * W + CALIB_BLOCK - 1) // CALIB_BLOCK)
 
 
+class RiskArgs(C.Structure):
+    _fields_ = [("net_out", vp), ("noisy", vp), ("noise_param", vp), ("est_raw", vp), ("pme", vp), ("ext", vp), ("B", i32), ("C", i32),
+                ("H", i32), ("W", i32), ("style", i32), ("mode", i32), ("diag", i32), ("margin", i32), ("stats", vp), ("scratch", vp),
+                ("scratch_bytes", C.c_int64)]
+
+
+RISK_BLOCK, RISK_NSTATS = 256, 12      # SSDN_RISK_BLOCK / SSDN_RISK_NSTATS
+
+
+def risk_scratch_bytes(B: int, Cn: int, H: int, W: int) -> int:
+    """SSDN_RISK_SCRATCH_BYTES of include/ssdn_hip.h: twelve 8-byte values per (sample, workgroup of RISK_BLOCK pixels)"""
+    return 8 * RISK_NSTATS * B * ((H * W + RISK_BLOCK - 1) // RISK_BLOCK)
+
+
 class ImageInArgs(C.Structure):
     _fields_ = [("src", vp), ("src_bytes", C.c_int64), ("offs", vp), ("ext", vp), ("B", i32), ("C", i32), ("H", i32), ("W", i32),
                 ("dst", vp)]
@@ -260,7 +274,7 @@ ARG_TYPES = dict(pack_input=PackInputArgs, conv=ConvArgs, pool_fwd=PoolArgs, poo
                  head_posterior=HeadPosteriorArgs, ssim=SsimArgs, calibration=CalibrationArgs, image_in=ImageInArgs, image_out=ImageOutArgs,
                  noise_est=NoiseEstArgs, tile_in=TileInArgs, tile_out=TileOutArgs, pool_patch=PoolPatchArgs,
                  image_in16=ImageIn16Args, image_out16=ImageOut16Args, tile_in16=TileIn16Args, tile_out16=TileOut16Args,
-                 pool_patch16=PoolPatch16Args)
+                 pool_patch16=PoolPatch16Args, risk=RiskArgs)
 
 # every symbol include/ssdn_hip.h declares
 ABI_VERSION = 19      # SSDN_ABI_VERSION of include/ssdn_hip.h this binding mirrors

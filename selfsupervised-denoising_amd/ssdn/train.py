@@ -46,6 +46,7 @@ from ssdn.utils import Metric, MetricDict, TrackedTime, separator
 
 logger = logging.getLogger("ssdn.train")
 _SSIM_CACHE = "_ssim_per_sample"          # ... and of the per-sample SSIM values of an evaluation with DenoiserTrainer.ssim set
+_RISK_CACHE = "_risk_per_sample"          # ... and of the per-sample reference-free risk values with DenoiserTrainer.risk set
 _CALIB_CACHE = "_calibration_per_sample"  # ... and of the per-sample calibration values with DenoiserTrainer.calibration set
 _POSTERIOR_COV = "_posterior_cov"         # (an output dict may bring the posterior covariance [B, C(C+1)/2, H, W] along: the path without a GPU)
 CALIB_METRICS = ("nll", "maha", "rmse_ratio", "cover_2s")     # what an evaluation reports as calib_<name>
@@ -55,7 +56,12 @@ _PSNR_CACHE = "_psnr_per_sample"         # key of the per-sample PSNR values the
 NOISY_MODES = ("style", "auto")
 
 
-def check_noisy(cfg: Dict, noisy: Optional[str], augment: bool = False, pool_bytes: Optional[int] = None, white: Optional[int] = None):
+# what an evaluation with DenoiserTrainer.risk set (and a noisy validation) reports, and the ssdn.utils.risk_values entry each one is
+RISK_METRICS = (("psnr_out_est", "psnr_out_est"), ("psnr_mu_est", "psnr_mu_est"), ("nll_noisy", "nll"))
+
+
+def check_noisy(cfg: Dict, noisy: Optional[str], augment: bool = False, pool_bytes: Optional[int] = None, white: Optional[int] = None,
+                validation: Optional[str] = None):
     """Training on images that are already noisy (`DenoiserTrainer.noisy`, `--noisy`): ValueError, with what to do instead, for every
     combination that cannot work.  noisy: None (off), "style" (the images carry the corruption NOISE_STYLE describes, its number is the
     known parameter) or "auto" (the parameter of every image is estimated once, when the pool is built).  white (`--white`): the sample
@@ -63,6 +69,9 @@ def check_noisy(cfg: Dict, noisy: Optional[str], augment: bool = False, pool_byt
     is built, which then refuses what does not fit (`--white` with 8-bit images, `--noisy auto` with 16-bit ones)."""
     from ssdn.utils import noise
     if not noisy:
+        if validation:
+            raise ValueError("--noisy_validation scores held-out images that are already noisy, as the training images of --noisy are: "
+                             "it needs --noisy (a validation set of clean images goes to -v)")
         if white is not None:
             raise ValueError("--white is the white level of a 16-bit noisy-image pool: it needs --noisy")
         if augment:
@@ -165,6 +174,14 @@ class DenoiserTrainer:
         self.noisy: Optional[str] = None
         self.augment = False
         self.pool_bytes: Optional[int] = None
+        # evaluation also reports the reference-free risk estimate (`ssdn eval --risk`, SSDN gauss / poisson models): psnr_out_est,
+        # psnr_mu_est, nll_noisy -- on a clean dataset the estimate then stands next to the true psnr_out
+        self.risk = False
+        self.risk_margin = 16
+        # `--noisy_validation PATH`: a folder or file of held-out NOISY images, scored at every EVAL_INTERVAL with Denoiser.denoise(risk=True)
+        # (no clean image anywhere); part of the "noisy" key of a `.training` file only when set
+        self.noisy_validation: Optional[str] = None
+        self._nv_images = None
         self.white: Optional[int] = None         # `--white`: the white level of a 16-bit pool (None: 65535); part of the "noisy" key only when given
 
     # ---- target -----------------------------------------------------------------------------------------------------------
@@ -233,6 +250,8 @@ class DenoiserTrainer:
             logger.info("Loading Validation Dataset...")
             self.testloader, self.testset, self.test_sampler = self.test_data()
             logger.info("Loaded Validation Dataset.")
+        if self.noisy_validation:
+            self._load_noisy_validation()
         if self.world > 1 and self._exchange is None:
             self._exchange = denoiser.gradient_exchange(self.world)
         K = int(self.accumulate)
@@ -258,6 +277,8 @@ class DenoiserTrainer:
             iteration = self.state[StateValue.ITERATION]
             if iteration % self.cfg[ConfigValue.EVAL_INTERVAL] == 0 and self.testloader is not None:
                 self._evaluate(self.testloader, output_callback=self.validation_output_callback(0))
+            if iteration % self.cfg[ConfigValue.EVAL_INTERVAL] == 0 and self._nv_images is not None:
+                self._noisy_validate()
             if iteration % self.cfg[ConfigValue.PRINT_INTERVAL] == 0:
                 self._flush_device_metrics()
                 history[HistoryValue.TIMINGS]["total"].update()
@@ -350,9 +371,90 @@ class DenoiserTrainer:
                         eval_history["calib_" + name] += cal[name]
                     total = cal["hist"].sum(0)
                     self.calibration_hist = total if idx == 0 or self.calibration_hist is None else self.calibration_hist + total
+                if self.risk:
+                    outputs[_RISK_CACHE] = rk = self.denoiser.risk(data, margin=self.risk_margin)
+                    self._add_risk(eval_history, rk)
                 if output_callback:
                     output_callback(idx, outputs)
                 idx += image_count
+
+    @staticmethod
+    def _add_risk(eval_history, values: Dict) -> None:
+        """the three reported risk values of some images into the evaluation history; an image without an estimate (NaN: too small, or
+        an estimate <= 0) is left out of that mean"""
+        for name, key in RISK_METRICS:
+            v = torch.as_tensor(values[key], dtype=torch.float64).reshape(-1)
+            v = v[~torch.isnan(v)]
+            if v.numel():
+                eval_history[name] += v.to(torch.float32)
+
+    def _load_noisy_validation(self) -> None:
+        """`--noisy_validation`: the held-out noisy images, loaded once on rank 0 through ssdn.utils.load_image; they must be of the
+        pool's depth.  A model without the risk estimate is refused here, when training starts."""
+        check_noisy(self.cfg, self.noisy, self.augment, self.pool_bytes, self.white, self.noisy_validation)
+        self.denoiser.check_risk("--noisy_validation")
+        if self.rank != 0:
+            return
+        from ssdn.datasets.folder import is_image_file
+        path = os.path.expanduser(self.noisy_validation)
+        if os.path.isfile(path) and is_image_file(path):
+            files = [path]
+        elif os.path.isdir(path):
+            files = UnlabelledImageFolderDataset(path, recursive=True).files
+        else:
+            raise FileNotFoundError("--noisy_validation: no such image file or folder: %s" % path)
+        ch = self.cfg[ConfigValue.IMAGE_CHANNELS]
+        images = []
+        for f in files:
+            a = ssdn.utils.load_image(f, ch)
+            images.append(a[:, :, 0] if a.shape[2] == 1 else a)
+        pool = getattr(self.trainloader, "pool", None)
+        bits = getattr(pool, "bits", None)
+        for f, a in zip(files, images):
+            if bits is not None and (16 if a.dtype.itemsize == 2 else 8) != bits:
+                raise ValueError("--noisy_validation: %s is a %d-bit image and the training pool holds %d-bit images: the held-out images must "
+                                 "be of the pool's depth" % (f, 8 * a.dtype.itemsize, bits))
+        if not images:
+            raise ValueError("--noisy_validation: no image under %s" % path)
+        self._nv_images = images
+        logger.info("Noisy validation: %d images from %s" % (len(images), path))
+
+    def _noisy_validation_param(self):
+        """the noise_param Denoiser.denoise takes for the held-out noisy images, as the training mode has it: the style's number for a
+        known-noise model, "auto" with `--noisy auto`, None for a model that reads none"""
+        from ssdn.utils import noise
+        cfg = self.cfg
+        if cfg.get(ConfigValue.NOISE_VALUE) != NoiseValue.KNOWN:
+            return None
+        if self.noisy == "auto":
+            return "auto"
+        kind, params, _ = noise.parse_style(cfg[ConfigValue.NOISE_STYLE])
+        return params[0]
+
+    def _noisy_validate(self) -> Optional[Dict]:
+        """One pass over the held-out noisy images (rank 0): Denoiser.denoise(risk=True) in batches of TEST_MINIBATCH_SIZE; psnr_out_est,
+        psnr_mu_est and nll_noisy go into the evaluation history (the VALID line, the scalars under valid/), the first image's output
+        under val_imgs/."""
+        if self.rank != 0 or self._nv_images is None:
+            return None
+        was_training = self.denoiser.training
+        res = self.denoiser.denoise(self._nv_images, noise_param=self._noisy_validation_param(),
+                                    batch_size=self.cfg[ConfigValue.TEST_MINIBATCH_SIZE], risk=True, risk_margin=self.risk_margin,
+                                    white=self.white if self._nv_images[0].dtype.itemsize == 2 else None)
+        self.denoiser.train(was_training)
+        eval_history = self.state[StateValue.HISTORY][HistoryValue.EVAL]
+        eval_history["n"] += len(self._nv_images)
+        self._add_risk(eval_history, {key: [r[key] for r in res["risk"]] for _, key in RISK_METRICS})
+        out_dir = os.path.join(self.run_dir_path, "val_imgs")
+        os.makedirs(out_dir, exist_ok=True)
+        name = os.path.join(out_dir, "{:08}_noisy-val_out.png".format(self.state[StateValue.ITERATION]))
+        first = res["out"][0]
+        if first.dtype == torch.uint16:
+            ssdn.utils.save_image16(first, name)
+        else:
+            from PIL import Image
+            Image.fromarray(first.numpy()).save(name)
+        return res
 
     # ---- outputs ----------------------------------------------------------------------------------------------------------
     def validation_output_callback(self, output_index: int) -> Callable:
@@ -422,7 +524,7 @@ class DenoiserTrainer:
     @staticmethod
     def _metric_strs(md) -> list:
         # (an SSIM lives in [-1, 1], a calibration value near 1: four decimals where the other metrics print two)
-        return [("{}={:8.4f}" if str(k).startswith(("ssim", "calib_")) else "{}={:8.2f}").format(k, float(torch.as_tensor(m.accumulated()).float().mean()))
+        return [("{}={:8.4f}" if str(k).startswith(("ssim", "calib_", "nll_")) else "{}={:8.2f}").format(k, float(torch.as_tensor(m.accumulated()).float().mean()))
                 for k, m in md.items() if isinstance(m, Metric) and not m.empty()]
 
     def train_state_str(self) -> str:
@@ -565,6 +667,8 @@ class DenoiserTrainer:
             sd["noisy"] = {"mode": self.noisy, "augment": bool(self.augment), "pool_bytes": self.pool_bytes}
             if self.white is not None:           # (an 8-bit run's file keeps exactly its keys)
                 sd["noisy"]["white"] = int(self.white)
+            if self.noisy_validation:            # (a run without it keeps exactly its keys)
+                sd["noisy"]["validation"] = str(self.noisy_validation)
         if int(self.accumulate) > 1:             # (a K = 1 file keeps the key set it always had)
             sd["accumulate"] = int(self.accumulate)
         return sd
@@ -582,6 +686,7 @@ class DenoiserTrainer:
         noisy = state_dict.get("noisy") or {}
         self.noisy, self.augment, self.pool_bytes = noisy.get("mode"), bool(noisy.get("augment", False)), noisy.get("pool_bytes")
         self.white = noisy.get("white")
+        self.noisy_validation = noisy.get("validation")
         torch.set_rng_state(state_dict["rng"])
         if self.world > 1 and self.rank > 0:
             # the file holds rank 0's generator state: the other ranks continue from a state derived from it, not from a copy

@@ -193,6 +193,150 @@ def calculate_calibration(mean: Tensor, cov: Tensor, ref: Tensor, hist: bool = F
     return res
 
 
+# ---- a reference-free risk estimate (SSDN_OP_RISK, csrc/risk.hip) ----------------------------------------------------------------
+RISK_NSTATS = 12
+RISK_VALUES = ("mse_mu_est", "mse_out_est", "psnr_mu_est", "psnr_out_est", "mse_mu_se", "mse_out_se", "nll", "weight", "clipped",
+               "degenerate")
+
+
+def risk_values(stats: Tensor, channels: int) -> Dict[str, Tensor]:
+    """The reported values from the raw statistics [..., 12] (float64) of calculate_risk / SSDN_OP_RISK.  With N = s0, sum q_mu = s4 - s6
+    and sum q_out = s5 + s7:  mse_mu_est = (s4 - s6) / (N C), mse_out_est = (s5 + s7) / (N C): unbiased estimates of the mean squared
+    error of the prior mean and of the delivered output against the clean image nobody has;  psnr_*_est = -10 log10 of them, NaN where
+    the estimate is <= 0 (it is unbiased, not positive: a small image can give that);  mse_*_se = sqrt((sum q^2 - (sum q)^2 / N) /
+    (N (N - 1))) / C, the naive standard error (pixels treated as independent);  nll = (s2 + s3) / (2 N C) + ln(2 pi) / 2, nats per
+    pixel-channel of the NOISY image under the model's marginal N(mu_x, Sigma_x + Sigma_n);  weight = s10 / (N C), how much of its own
+    noisy value a pixel's output keeps;  clipped = s11 / (N C);  degenerate = s1 / (s0 + s1).  N < 2: the ratios are NaN."""
+    s = stats.to(torch.float64)
+    nan = torch.full_like(s[..., 0], float("nan"))
+    n, deg = s[..., 0], s[..., 1]
+    some = n >= 2
+    nn = torch.where(some, n, nan)
+    nc = nn * channels
+    res = {}
+    for name, sq, sq2 in (("mu", s[..., 4] - s[..., 6], s[..., 8]), ("out", s[..., 5] + s[..., 7], s[..., 9])):
+        mse = sq / nc
+        res["mse_%s_est" % name] = mse
+        res["psnr_%s_est" % name] = torch.where(mse > 0, -10.0 * torch.log10(torch.where(mse > 0, mse, torch.ones_like(mse))), nan)
+        var = (sq2 - sq * sq / nn) / (nn * (nn - 1))
+        res["mse_%s_se" % name] = torch.sqrt(torch.clamp(var, min=0.0)) / channels
+    res["nll"] = 0.5 * (s[..., 2] + s[..., 3]) / nc + 0.5 * math.log(2 * math.pi)
+    res["weight"] = s[..., 10] / nc
+    res["clipped"] = s[..., 11] / nc
+    res["degenerate"] = torch.where(n + deg > 0, deg / torch.where(n + deg > 0, n + deg, nan), nan)
+    return {k: res[k] for k in RISK_VALUES}
+
+
+def calculate_risk(noisy: Tensor, mu: Tensor, cov_x: Tensor, out: Tensor, noise_var: Tensor, var_hat: Tensor, ext=None, margin: int = 0,
+                   maps: bool = False) -> Dict[str, Tensor]:
+    """A reference-free estimate of the squared error of a blind-spot model's two outputs -- the specification SSDN_OP_RISK
+    (csrc/risk.hip) is held to, float64 on any device.  The prior (mu, Sigma_x) at a pixel depends on the OTHER pixels only and the
+    output is affine in the pixel's own noisy value y, out = mu + W (y - mu), W = Sigma_x (Sigma_x + Sigma_n)^-1; for zero-mean noise,
+    independent across pixels and channels with variances v_c,
+        E|mu - x|^2 = E[ |mu - y|^2 - sum_c v_c ],        E|out - x|^2 = E[ |out - y|^2 + sum_c (2 W_cc - 1) v_c ].
+    noisy, mu, out, noise_var (n_c, the model's noise variance), var_hat (v^_c, an unbiased stand-in of v_c): [B,C,H,W]; cov_x:
+    [B, C(C+1)/2, H, W], upper triangle 00, 01, 02, 11, 12, 22; C in {1, 3}.  Per pixel, in float64 from the inputs as they are, in this
+    fixed order (C = 3), T = Sigma_x + diag(n_c), d = y - mu:
+        p0 = t00, l00 = sqrt p0, l10 = t01 / l00, l20 = t02 / l00;  p1 = t11 - l10^2, l11 = sqrt p1, l21 = (t12 - l20 l10) / l11;
+        p2 = t22 - l20^2 - l21^2, l22 = sqrt p2;  w0 = d0 / l00, w1 = (d1 - l10 w0) / l11, w2 = (d2 - l20 w0 - l21 w1) / l22;
+        d2 = w0^2 + w1^2 + w2^2, logdet = ln p0 + ln p1 + ln p2        (calculate_calibration's spelling, for T);
+        Li00 = 1 / l00, Li11 = 1 / l11, Li22 = 1 / l22, Li10 = -(l10 Li00) / l11, Li21 = -(l21 Li11) / l22,
+        Li20 = -(l20 Li00 + l21 Li10) / l22;  t00' = Li00^2 + Li10^2 + Li20^2, t11' = Li11^2 + Li21^2, t22' = Li22^2  (diagonal of T^-1);
+        W_cc = 1 - n_c t_cc'                     (C = 1: W = 1 - n / (s + n), d2 = d^2 / (s + n), logdet = ln(s + n));
+        q_mu = sum_c (mu_c - y_c)^2 - sum_c v^_c,      q_out = sum_c (out_c - y_c)^2 + sum_c (2 W_cc - 1) v^_c.
+    A pixel is valid iff all its inputs are finite and every pivot is > 0; a degenerate pixel is counted and left out of everything
+    else.  Only the pixels margin <= i < e1 - margin, margin <= j < e2 - margin of a sample's extent ext[b] = (e1, e2) (None: the whole
+    tensor; clamped to it) take part.  There is no 1e-6 regulariser: the heads place theirs differently, far below the estimator's
+    resolution wherever n_c >> 1e-6.
+    -> {"stats": float64 [B,12]: N, degenerate, sum d2, sum logdet, sum |mu - y|^2, sum |out - y|^2, sum sum_c v^_c,
+    sum sum_c (2 W_cc - 1) v^_c, sum q_mu^2, sum q_out^2, sum tr W, the (valid pixel, channel) pairs with y_c <= 0 or y_c >= 1 (clipped
+    samples, where the noise is not zero-mean: reported, not removed -- removing them would select)} and the values `risk_values`
+    derives, float64 [B] each.  maps=True adds "q_mu" and "q_out" [B,H,W], NaN outside the region and at degenerate pixels."""
+    if noisy.dim() != 4 or noisy.shape[1] not in (1, 3):
+        raise ValueError("calculate_risk: noisy must be BCHW with C in {1, 3}, got %s" % (tuple(noisy.shape),))
+    B, C, H, W = noisy.shape
+    for name, t in (("mu", mu), ("out", out), ("noise_var", noise_var), ("var_hat", var_hat)):
+        if tuple(t.shape) != (B, C, H, W):
+            raise ValueError("calculate_risk: %s must be %s, got %s" % (name, (B, C, H, W), tuple(t.shape)))
+    if tuple(cov_x.shape) != (B, C * (C + 1) // 2, H, W):
+        raise ValueError("calculate_risk: cov_x must be %s, got %s" % ((B, C * (C + 1) // 2, H, W), tuple(cov_x.shape)))
+    if int(margin) < 0:
+        raise ValueError("calculate_risk: margin must be at least 0, got %s" % (margin,))
+    margin = int(margin)
+    dev = noisy.device
+    y, m, s, o, n, v = (t.to(torch.float64) for t in (noisy, mu, cov_x, out, noise_var, var_hat))
+    fin = torch.ones((B, H, W), dtype=torch.bool, device=dev)
+    for t in (y, m, s, o, n, v):
+        fin = fin & torch.isfinite(t).all(1)
+    if ext is None:
+        e = torch.tensor([[H, W]] * B, dtype=torch.int64, device=dev)
+    else:
+        e = torch.as_tensor(ext, device=dev).to(torch.int64).reshape(B, 2)
+    e1 = e[:, 0].clamp(0, H)[:, None, None]
+    e2 = e[:, 1].clamp(0, W)[:, None, None]
+    ii = torch.arange(H, device=dev)[None, :, None]
+    jj = torch.arange(W, device=dev)[None, None, :]
+    region = (ii >= margin) & (ii < e1 - margin) & (jj >= margin) & (jj < e2 - margin)
+    d = y - m
+    if C == 3:
+        n0, n1, n2 = n[:, 0], n[:, 1], n[:, 2]
+        t00, t01, t02, t11, t12, t22 = s[:, 0] + n0, s[:, 1], s[:, 2], s[:, 3] + n1, s[:, 4], s[:, 5] + n2
+        p0 = t00
+        l00 = torch.sqrt(p0)
+        l10, l20 = t01 / l00, t02 / l00
+        p1 = t11 - l10 * l10
+        l11 = torch.sqrt(p1)
+        l21 = (t12 - l20 * l10) / l11
+        p2 = (t22 - l20 * l20) - l21 * l21
+        l22 = torch.sqrt(p2)
+        w0 = d[:, 0] / l00
+        w1 = (d[:, 1] - l10 * w0) / l11
+        w2 = ((d[:, 2] - l20 * w0) - l21 * w1) / l22
+        d2 = (w0 * w0 + w1 * w1) + w2 * w2
+        logdet = (torch.log(p0) + torch.log(p1)) + torch.log(p2)
+        li00, li11, li22 = 1.0 / l00, 1.0 / l11, 1.0 / l22
+        li10 = -(l10 * li00) / l11
+        li21 = -(l21 * li11) / l22
+        li20 = -(l20 * li00 + l21 * li10) / l22
+        ti = ((li00 * li00 + li10 * li10) + li20 * li20, li11 * li11 + li21 * li21, li22 * li22)
+        wcc = [1.0 - n[:, c] * ti[c] for c in range(3)]
+        valid = fin & (p0 > 0) & (p1 > 0) & (p2 > 0)
+    else:
+        p0 = s[:, 0] + n[:, 0]
+        d2 = (d[:, 0] * d[:, 0]) / p0
+        logdet = torch.log(p0)
+        wcc = [1.0 - n[:, 0] / p0]
+        valid = fin & (p0 > 0)
+
+    def over(f):                        # a per-pixel sum over the channels, left to right
+        acc = f(0)
+        for c in range(1, C):
+            acc = acc + f(c)
+        return acc
+    em = over(lambda c: (m[:, c] - y[:, c]) * (m[:, c] - y[:, c]))
+    eo = over(lambda c: (o[:, c] - y[:, c]) * (o[:, c] - y[:, c]))
+    sv = over(lambda c: v[:, c])
+    sw = over(lambda c: (2.0 * wcc[c] - 1.0) * v[:, c])
+    trw = over(lambda c: wcc[c])
+    q_mu, q_out = em - sv, eo + sw
+    valid = valid & region
+    clipped = over(lambda c: ((y[:, c] <= 0.0) | (y[:, c] >= 1.0)).to(torch.float64))
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+
+    def total(t):
+        return torch.where(valid, t, zero).reshape(B, -1).sum(1)
+    cols = [valid.reshape(B, -1).sum(1).to(torch.float64), (region & ~valid).reshape(B, -1).sum(1).to(torch.float64), total(d2),
+            total(logdet), total(em), total(eo), total(sv), total(sw), total(q_mu * q_mu), total(q_out * q_out), total(trw), total(clipped)]
+    stats = torch.stack(cols, 1)
+    res = {"stats": stats}
+    res.update(risk_values(stats, C))
+    if maps:
+        nan = torch.full_like(q_mu, float("nan"))
+        res["q_mu"] = torch.where(valid, q_mu, nan)
+        res["q_out"] = torch.where(valid, q_out, nan)
+    return res
+
+
 # ---- blind noise-level estimation (SSDN_OP_NOISE_EST, csrc/noise_est.hip) -------------------------------------------------------
 NOISE_EST_CLASSES, NOISE_EST_BINS, NOISE_EST_NMIN = 8, 1024, 256
 NOISE_EST_C = 6 * 0.6744897501960817             # |r| has standard deviation 6 sigma; the median of |N(0, 1)| is 0.6744...
